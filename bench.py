@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s of the continuous wavelet transform.
 
-    python bench.py --gpus N --steps K --warmup W [--config 3|5]
+    python bench.py --gpus N --steps K --warmup W [--config 3|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps and prints the result line (`ms_per_step`: one
+timed step; `roofline`: from the HIP events the timed steps themselves carry).  Everything else the
+bench measures or checks runs with --full only: the HBM ceilings (before the timed steps), package power
+(during them) and, after them, the stage breakdown, the oracle and whole-output checks, the complex-output
+mode, configs 1, 2, 5 and the heavy-tailed wavelet, and the CPU baseline (the --no-* switches trim it).
+--dump-outputs DIR: after the timed steps, a fixed, seeded sample of what the last one left in the
+result buffer goes to DIR as float32 .npy files (dump_outputs); the inputs are seeded, so two builds
+given the same arguments can be compared output for output.
 
 --config 3 (default; BASELINE.json configs[2], and configs[3] at N = 8): 128 channels per
 GPU x 1e6 samples @ 1 kHz x 100 Morse scales (log-spaced 200..2 Hz), amplitude output,
@@ -289,6 +298,41 @@ def full_output_check(obuf, C, N, S, distinct, output="amplitude"):
             "ok": bad.value == 0 and diff.value == 0}
 
 
+DUMP_SEED = 20261016
+DUMP_ROWS_BYTES = 40 << 20                          # whole rows (channel, scale)
+DUMP_WINDOW_BYTES = 16 << 20                        # every row over a short run of samples
+
+
+def dump_outputs(dirname, name, buf, shape, pitch, is_complex):
+    """--dump-outputs: a fixed, seeded sample of a (C, S, n) result left in device buffer `buf` (rows `pitch`
+    samples apart; complex64 when `is_complex`, else float32), 56 MB at most, as float32 .npy files in `dirname`:
+      <name>_rows.npy    (R, m): R whole rows (row r = channel r // S, scale r % S) drawn without replacement,
+                         in increasing order -- rows of more than 10 M samples: the same seeded run of m of each;
+      <name>_window.npy  (C, S, w): every row over w samples from a seeded offset.
+    Complex results carry a last axis of 2 (real, imaginary).  The sample depends on the shape alone."""
+    import ctypes
+    from ghost_amd._lib import lib, check
+    C, S, n = shape
+    k = 2 if is_complex else 1
+    rng = np.random.default_rng(DUMP_SEED)
+    cols = min(n, DUMP_ROWS_BYTES // (4 * k))
+    n_rows = min(C * S, DUMP_ROWS_BYTES // (4 * k * cols))
+    rows = np.sort(rng.choice(C * S, n_rows, replace=False))
+    a = int(rng.integers(0, n - cols + 1))
+    got = np.stack([buf.download((cols * k,), np.float32, offset_bytes=4 * k * (int(r) * pitch + a)) for r in rows])
+    w = max(1, min(n, DUMP_WINDOW_BYTES // (4 * k * C * S)))
+    if C * S * w * 4 * k > DUMP_WINDOW_BYTES:
+        raise SystemExit("--dump-outputs: %d x %d rows do not fit the window's %d MB" % (C, S, DUMP_WINDOW_BYTES >> 20))
+    b = int(rng.integers(0, n - w + 1))
+    win = np.empty((C * S, w * k), np.float32)
+    check(lib.gcwt_rows_to_host(ctypes.c_void_p(buf.ptr.value + 4 * k * b), pitch * k, C * S, w * k,
+                                win.ctypes.data_as(ctypes.c_void_p), w * k, 0))
+    tail = (2,) if is_complex else ()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + "_rows.npy"), got.reshape((n_rows, cols) + tail))
+    np.save(os.path.join(dirname, name + "_window.npy"), win.reshape((C, S, w) + tail))
+
+
 # ----------------------------------------------------------------------------
 # one rank
 # ----------------------------------------------------------------------------
@@ -365,7 +409,7 @@ def run_rank(args):
 
     # what this box's HBM delivers (measured once, before anything is timed)
     ceilings = {}
-    if rank == 0 and not args.no_ceilings:
+    if rank == 0 and args.full and not args.no_ceilings:
         # store_pattern_ceiling: k_synthi's own pattern (1 KB runs per wave, 53 KB visits; round 4) -- the kernel that
         # writes 63 of the 100 scales; store_pattern_ceiling_synth7: k_synth7's 128-byte runs (rounds 1-3's probe)
         for key, pat in (("peak_measured_copy", 1), ("peak_measured_fill", 0), ("store_pattern_ceiling", 3),
@@ -424,7 +468,7 @@ def run_rank(args):
         bus = buf.value.decode()
     except Exception:
         pass
-    sampler = PowerSampler(pci_bus_id=bus) if rank == 0 else None
+    sampler = PowerSampler(pci_bus_id=bus) if rank == 0 and args.full else None
     comm.barrier()
     stats = {}
     if sampler:
@@ -438,6 +482,15 @@ def run_rank(args):
     elapsed = time.perf_counter() - t0
     power = sampler.stop() if sampler else None
     elapsed = comm.allreduce_max(elapsed)
+    if args.dump_outputs:                            # what the last timed step left, before anything runs again
+        tag = "" if world == 1 else "_rank%d" % rank
+        if cfg5:                                     # the ring holds the last two blocks: the last one's result
+            a, b, _ = segs[-1]
+            k_last = (C // group) * len(segs) - 1
+            dump_outputs(args.dump_outputs, args.output + "_last_block" + tag, ring[k_last & 1],
+                         (group, S, b - a), b - a, args.output == "complex")
+        else:
+            dump_outputs(args.dump_outputs, args.output + tag, obuf, (C, S, N), N, args.output == "complex")
     sustained = None
     if rank == 0 and world == 1 and power and args.sustain > 0:
         # hwmon's power reading is a moving average that lags a 0.1 s burst: the same step is run
@@ -457,11 +510,12 @@ def run_rank(args):
             sustained["steps"], sustained["seconds"] = n_s, round(time.perf_counter() - t_s, 2)
     # the stage breakdown: the same step again with every stage between events, after and outside the timed region
     stage_stats, n_stage_steps = {}, min(args.steps, 10)
-    plan.set_profiling(True)
-    for i in range(n_stage_steps + 1):
-        step(stage_stats if i > 0 else {})               # (the first one after the switch is not counted)
-    check(lib.gcwt_device_synchronize())
-    plan.set_profiling(2)
+    if args.full:
+        plan.set_profiling(True)
+        for i in range(n_stage_steps + 1):
+            step(stage_stats if i > 0 else {})           # (the first one after the switch is not counted)
+        check(lib.gcwt_device_synchronize())
+        plan.set_profiling(2)
     per_rank = comm.allgather(own / args.steps * 1e3)
     devices = comm.allgather(dev)
     numas = comm.allgather(-1 if numa is None else numa)
@@ -516,14 +570,15 @@ def run_rank(args):
                          "traffic": traffic, "traffic_source": traffic_src,
                          "kernel_ms": round(k_ms, 4), "launches_per_step": launches // args.steps,
                          "algorithmic_bytes": int(alg_launch), **ceilings},
-            # every stage between HIP events, over `stages_steps` further steps after the timed region (their events
-            # slow a step by ~0.19 ms: `total_ms` here is longer than `ms_per_step`); the timed steps themselves
-            # bracket the synthesis kernels only (`roofline.kernel_ms`)
-            "stages_ms": {k: round(float(v) / n_stage_steps, 4) for k, v in stage_stats.items() if k.endswith("_ms")},
-            "stages_steps": n_stage_steps,
             "timed_region_events": "synthesis kernels only (gcwt_plan_set_profiling level 2)",
             "whole_job_frac_of_hbm_peak": round(alg_step * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 4),
         }
+        if args.full:
+            # every stage between HIP events, over `stages_steps` further steps after the timed region (their events
+            # slow a step by ~0.19 ms: `total_ms` here is longer than `ms_per_step`); the timed steps themselves
+            # bracket the synthesis kernels only (`roofline.kernel_ms`)
+            line["stages_ms"] = {k: round(float(v) / n_stage_steps, 4) for k, v in stage_stats.items() if k.endswith("_ms")}
+            line["stages_steps"] = n_stage_steps
         rl = line["roofline"]
         if info["n_interp"]:
             # the two synthesis kernels apart: rows x samples x 4 B each wrote, over its own launch time
@@ -556,7 +611,7 @@ def run_rank(args):
                 "sclk_ghz_mean": ref["sclk_ghz"], "sclk_ghz_max": 2.4,
                 "frac_of_store_pattern_ceiling": round(achieved / ceilings["store_pattern_ceiling"], 4) if ceilings else None,
                 "study": "profiles/r06_bound.md"}
-        else:
+        elif args.full:
             rl["power_w"] = rl["sclk_ghz"] = rl["limits_measured"] = None   # no readable hwmon
         if not cfg5:
             # SURVEY.md 8d's secondary ceiling, fp32 vector flops.  `reference_method_*`: what the
@@ -588,10 +643,10 @@ def run_rank(args):
                              "devices": [int(d) for d in devices],
                              "numa_nodes": [int(v) for v in numas],   # -1: not pinned (sysfs silent or outside the affinity)
                              "pinned_cpus_rank0": n_pinned}
-        if cfg5 and not args.no_check:
+        if args.full and cfg5 and not args.no_check:
             line["checked"], line["check"] = check_config5(plan, xbuf, ring[0], base, distinct, fs, freqs, N, S,
                                                            group, segs)
-        if not cfg5 and not args.no_check:
+        if args.full and not cfg5 and not args.no_check:
             dec = plan.scale_info()["decimation"]
             ok, worst = spot_check(obuf, base, fs, freqs, C, N, distinct, output=args.output, dec=dec)
             full = full_output_check(obuf, C, N, S, distinct, output=args.output)
@@ -600,7 +655,7 @@ def run_rank(args):
                                      "decimation level) vs the oracle, tiled channels c / c+%d bit-equal"
                                      % (check_scales(S, dec), distinct),
                              "worst_rel_err": float("%.3g" % worst), "full_output": full}
-        if world == 1 and not cfg5 and args.output == "amplitude" and not args.no_other_modes:
+        if args.full and world == 1 and not cfg5 and args.output == "amplitude" and not args.no_other_modes:
             # Secondary measurement, after and outside the timed region: the same workload with the
             # complex coefficients stored (8 B per coefficient: SURVEY.md 8d's second target).
             obuf.free()
@@ -608,7 +663,7 @@ def run_rank(args):
             line["other_modes"] = {"complex": other_mode("complex", N, C, fs, freqs, S, xbuf, dev, lib, check,
                                                          steps=args.steps, warmup=args.warmup,
                                                          check_against=None if args.no_check else (base, distinct))}
-        if world == 1 and not cfg5 and not args.no_other_configs:
+        if args.full and world == 1 and not cfg5 and not args.no_other_configs:
             # BASELINE.json's configs 2 and 5, after and outside the timed region, so that the driver's run
             # carries them too (round 3: builder-run only).  Everything of the headline is released first.
             for b in (locals().get("obuf"), xbuf):
@@ -625,7 +680,7 @@ def run_rank(args):
                                      "heavy_tailed_wavelet": heavy_tail_leg(N, C, fs, freqs, dev, lib, check,
                                                                             no_check=args.no_check),
                                      "config5": config5_leg(args)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(fs, freqs)
         emit(line)
     comm.close()
@@ -852,7 +907,7 @@ def config5_leg(args):
     """BASELINE.json config 5 per GPU (48 of its 384 channels), 3 timed steps and the config-5 check, as a
     child process that runs after this one has released the device: its JSON line, trimmed."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", "5", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", "5", "--steps", "3", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--no-ceilings", "--sustain", "0"]
     if args.no_check:
         cmd.append("--no-check")
@@ -936,9 +991,17 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the config-2 and config-5 legs after the timed steps")
     ap.add_argument("--no-cooldown", action="store_true", help="config-2 public-call leg: do not wait for the link to recover after the timed steps")
     ap.add_argument("--no-other-modes", action="store_true", help="skip the complex-output measurement after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the headline does not need: HBM ceilings, power, and after the timed steps the "
+                         "stage breakdown, checks against the oracle, the complex mode, configs 1 / 2 / 5, the "
+                         "heavy-tailed wavelet, the CPU baseline (the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write a fixed, seeded sample (56 MB at most) of the last timed step's result to DIR/*.npy")
     ap.add_argument("--dry-run", default="", metavar="DIR",
                     help="launcher rehearsal: every rank writes DIR/rank<r>.json and exits (no GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])
     return run_rank(args)

@@ -1242,7 +1242,7 @@ def test_bench_runs_two_ranks_end_to_end(tmp_path):
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(GHOSTCWT_ALLOW_SHARED_GPU="1", GHOSTCWT_COMM="file", GHOSTCWT_RDZV_DIR=str(tmp_path))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                          "--warmup", "1", "--channels", "8", "--samples", "150000", "--no-cpu-baseline",
+                          "--warmup", "1", "--channels", "8", "--samples", "150000", "--full", "--no-cpu-baseline",
                           "--no-ceilings"], env=env, capture_output=True, timeout=600)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -1274,7 +1274,7 @@ def test_bench_shards_time_blocks_over_two_ranks(tmp_path):
     env.update(GHOSTCWT_ALLOW_SHARED_GPU="1", GHOSTCWT_COMM="file", GHOSTCWT_RDZV_DIR=str(tmp_path))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "5", "--shard", "time",
                           "--channels", "2", "--group", "2", "--samples", "6000000", "--max-fft-log2", "21",
-                          "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-ceilings", "--sustain", "0"],
+                          "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ceilings", "--sustain", "0"],
                          env=env, capture_output=True, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
@@ -1284,6 +1284,46 @@ def test_bench_shards_time_blocks_over_two_ranks(tmp_path):
     assert line["config"]["channels_total"] == 2 and "time-block-sharded x2" in line["config"]["parallelism"]
     # the whole job is the recording once, whatever the number of ranks
     assert line["value"] == pytest.approx(2 * 6000000 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the plain run times its K steps and
+    prints the headline line without the --full legs, and DIR holds float32 samples of the last timed step's
+    result (56 MB at most): whole rows, each one of the oracle's rows of the tiled recordings, and a window
+    over every row."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from ghost_amd.synthetic import lfp
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    C, N, S, fs = 8, 150000, 16, 1000.0
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--channels", str(C), "--samples", str(N), "--scales", str(S),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, timeout=600)
+    assert res.returncode == 0, res.stderr.decode()[-3000:]
+    lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(C * N / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for key in ("checked", "stages_ms", "other_modes", "other_configs", "cpu_baseline"):
+        assert key not in line, key
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["amplitude_rows.npy", "amplitude_window.npy"], files
+    rows, win = np.load(tmp_path / "out" / files[0]), np.load(tmp_path / "out" / files[1])
+    assert rows.dtype == win.dtype == np.float32 and rows.nbytes + win.nbytes <= 64 << 20
+    assert rows.shape[1] == N and win.shape[:2] == (C, S) and np.isfinite(win).all()
+    x = lfp(C, N, fs, seed=1234)                              # bench.py's recordings on rank 0 (8 distinct channels)
+    freqs = np.geomspace(200.0, 2.0, S)
+    ref = np.concatenate([orc.cwt_amplitude(x[c].astype(np.float64), fs, freqs) for c in range(C)])
+    seen = set()
+    for row in rows:
+        err = np.abs(ref - row).max(axis=1) / np.abs(ref).max(axis=1)
+        seen.add(int(np.argmin(err)))
+        assert err.min() < 1e-5, err.min()
+    assert len(seen) == len(rows)                             # distinct rows
 
 
 def test_split_levels_option(option):

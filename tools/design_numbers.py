@@ -21,7 +21,7 @@ gen = {}
 te = c2["transform_end_to_end"]
 cb = j["cpu_baseline"]
 gen["headline"] = (
-    "**Measured, round %s** (`profiles/%s_bench.json`, `tools/prof_round.sh %s`: `bench.py --steps 10 --warmup 2` on one MI355X;\n"
+    "**Measured, round %s** (`profiles/%s_bench.json`, `tools/prof_round.sh %s`: `bench.py --full --steps 10 --warmup 2` on one MI355X;\n"
     "boxes of the pool differ by 2 - 4 %%): synthesis %.2f ms from HIP events (k_synthi %.2f + k_synth7 %.2f) = %.2f TB/s =\n"
     "**%.4f** of the 8 TB/s peak (`roofline.frac`); rocprofv3 of the same command (`profiles/%s_kernel_stats.csv`, %d launches\n"
     "each): %.3f + %.3f = %.2f ms.  Whole step %.2f ms = **%.0f Msamples/s** = %.3f of the peak on algorithmic bytes (mean\n"

@@ -1,10 +1,10 @@
 """profiles/traffic.json and the round's rocprof summaries from the newest files that
-tools/prof_round.sh left under gpurun_out/<round>/.  Usage: python tools/traffic.py r01"""
+tools/prof_round.sh left under $PROF_OUT/<round>/ (default prof_out/<round>/).  Usage: python tools/traffic.py r01"""
 import collections, csv, glob, json, os, re, shutil, sys
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-src = os.path.join(root, "gpurun_out", rnd)
+src = os.path.join(root, os.environ.get("PROF_OUT", "prof_out"), rnd)
 
 
 def newest(pattern):
