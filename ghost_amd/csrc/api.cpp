@@ -232,7 +232,13 @@ struct gcwt_plan {
   hipGraphExec_t graph_exec = nullptr;
   bool graph_seen_valid = false, graph_failed = false;
   int64_t row_pitch = 0;     // device output rows, samples; 0 = dense
+  int64_t out_stride = 1;    // K: output column j holds recording sample K j (gcwt_plan_set_output_stride)
 };
+
+namespace {
+// output columns of the samples [a, b) of the recording: the multiples of K among them
+inline int64_t stride_cols(int64_t a, int64_t b, int64_t k) { return b <= a ? 0 : (b + k - 1) / k - (a + k - 1) / k; }
+}  // namespace
 
 namespace {
 
@@ -525,7 +531,8 @@ int gcwt_plan_get_info(const gcwt_plan* plan, gcwt_plan_info* info) {
       if (sub && gcwt_plan_get_info(sub, &si) == GCWT_OK) info->workspace_bytes += si.workspace_bytes;
     }
   }
-  info->out_bytes = (int64_t)hp.out_elem_bytes * hp.prm.n_channels * hp.prm.n_freqs * hp.prm.n_samples;
+  info->out_bytes = (int64_t)hp.out_elem_bytes * hp.prm.n_channels * hp.prm.n_freqs *
+                    stride_cols(0, hp.prm.n_samples, plan->out_stride);
   return GCWT_OK;
 }
 
@@ -565,6 +572,17 @@ int gcwt_plan_set_profiling(gcwt_plan* plan, int enabled) {
 int gcwt_plan_set_row_pitch(gcwt_plan* plan, int64_t pitch_samples) {
   if (!plan || pitch_samples < 0) return set_err(GCWT_ERR_INVALID, "bad row pitch");
   plan->row_pitch = pitch_samples;
+  return GCWT_OK;
+}
+
+int gcwt_plan_set_output_stride(gcwt_plan* plan, int64_t stride) {
+  if (!plan) return set_err(GCWT_ERR_INVALID, "NULL plan");
+  if (stride < 1 || stride > 0x7fffffff) return set_err(GCWT_ERR_INVALID, "output stride must be an integer >= 1");
+  if (plan->uploaded) return set_err(GCWT_ERR_INVALID, "output stride set after the plan's first upload or execute");
+  // the strided stores find a sample's column with 32-bit arithmetic (kernels.h: stride_keep)
+  if (stride > 1 && plan->hp.prm.n_samples >= ((int64_t)1 << 31))
+    return set_err(GCWT_ERR_UNSUPPORTED, "output stride on recordings of 2^31 samples or more");
+  plan->out_stride = stride;
   return GCWT_OK;
 }
 
@@ -1022,6 +1040,10 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
   hipStream_t st = p->stream;
   hipError_t he;
   p->cur = nullptr;            // (an earlier call may have failed between a fork and its join)
+  // output stride K: sample n of the recording is column n / K - ceil(r0 / K) of a row, kept when K divides it
+  const int64_t K = p->out_stride;
+  const OutStride os = make_out_stride(K, r0);
+  const bool strided = K > 1;
 #define RUN(stage_id, call)                         \
   do {                                              \
     SpanGuard sg_(p, stage_id);                     \
@@ -1068,9 +1090,9 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       he = hipMemsetAsync(dout, 0, sizeof(float) * (size_t)elem * (size_t)row_len * (size_t)C * (size_t)S, st);
       if (he != hipSuccess) return hip_err(he, "zero fill");
     } else {
-      for (const auto& g : gaps) {
-        he = launch_zero_range(dout, row_len * elem, (int64_t)C * S, (g.first - r0) * elem,
-                               (g.second - g.first) * elem, st);
+      for (const auto& g : gaps) {     // (K > 1: the gap's columns, the multiples of K inside it)
+        he = launch_zero_range(dout, row_len * elem, (int64_t)C * S, stride_cols(r0, g.first, K) * elem,
+                               stride_cols(g.first, g.second, K) * elem, st);
         if (he != hipSuccess) return hip_err(he, "zero_range");
       }
     }
@@ -1111,6 +1133,7 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
     e0 += count;
     if (nb == 0) continue;
     sin.n_channels = sout.n_channels = psegs.n_channels = C;
+    sout.os = os;
     const int slots = C * nb;
     // P, P1: the STORED spectrum (rows of 4096 bins); Pt: the segment's true FFT length.  They differ in long mode
     // only (planner.h, EpochPlan::long_a: Pt = A P, the spectrum's low half combined from A interleaved transforms)
@@ -1301,7 +1324,8 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       if (dev.n_items_i > 65535) ai.channels_fastest = 0;       // (grid.y is 16 bits wide)
       ai.seg = sout;
       p->cur = si;
-      RUN(ST_INTERP, launch_synthi(mode, ai, dev.n_items_i, slots, si));
+      if (strided) RUN(ST_INTERP, launch_synthis(mode, ai, dev.n_items_i, slots, si));
+      else RUN(ST_INTERP, launch_synthi(mode, ai, dev.n_items_i, slots, si));
       p->cur = nullptr;
     }
     for (int k = 0; k < 2; ++k) {
@@ -1328,6 +1352,7 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       ap.seg = sout;
       p->cur = si;
 #ifdef GCWT_MEASURE
+      if (strided) return set_err(GCWT_ERR_UNSUPPORTED, "output stride with the pipelined interpolating kernel");
       RUN(ST_INTERP, launch_synthp(mode, ap, dev.n_items_p[k], slots, k == 1, si));
 #else
       return set_err(GCWT_ERR_INVALID, "internal: a level planned for the measure build's pipelined kernel");
@@ -1376,6 +1401,10 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
         a7.xr = p->d_xr;
         a7.xr_cstride = hp.max_xr;
         a7.xb_scale = (float)(1.0 / ((double)hp.block * (double)Pt));
+      }
+      if (strided) {                     // every halo width: the strided kernel tests each row's place in the block
+        RUN(ST_SYNTH, launch_synth7s(mode, cols7, a7, n7, slots, st));
+        continue;
       }
 #ifdef GCWT_MEASURE
       if (p->synth_kernel == 8 && variant == 1)
@@ -1483,7 +1512,7 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
     auto flush = [&]() -> int {
       if (ne > 0)
         RUN(ST_DIRECT, launch_direct(mode, dx, dout, p->d_psi, p->d_direct_sc, hp.n_direct, p->d_sums,
-                                     inv_n, N, S, eps, ne, r0, row_len, p->max_direct_len, p->d_psi_tail, st, dmask));
+                                     inv_n, N, S, eps, ne, r0, row_len, p->max_direct_len, p->d_psi_tail, st, dmask, os));
       ne = 0;
       return GCWT_OK;
     };
@@ -1525,7 +1554,7 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
           RUN(ST_BLOCKCONV, launch_bc_forward(dx, p->d_bc_x, bl, b0, nblk, N, p->d_tw64, p->d_sums, inv_n, st));
           RUN(ST_BLOCKCONV, launch_bc_scales(mode, p->d_bc_x, dout, p->d_bc_h + (int64_t)g.first * kRowLen,
                                              p->d_bc_rows + g.first, g.count, p->d_bc_tw, p->d_tw256, bl, b0, nblk,
-                                             S, r0, row_len, st, dmask));
+                                             S, r0, row_len, st, dmask, os));
         }
         ne = 0;
         return GCWT_OK;
@@ -1586,6 +1615,7 @@ static int reroute_scales(gcwt_plan* p, const float* dx, float* dout, int64_t ou
       return set_err(GCWT_ERR_INVALID, "internal: the exact sub-plan keeps a decimated scale");
     }
     sub->is_sub_plan = true;
+    sub->out_stride = p->out_stride;       // the rerouted rows land in the strided rows
     if ((rc = gcwt_plan_upload(sub))) { gcwt_plan_destroy(sub); sub = nullptr; return rc; }
     if (hipMalloc((void**)&sub->d_run_mask, (size_t)S) != hipSuccess) {
       (void)hipGetLastError();
@@ -1598,7 +1628,7 @@ static int reroute_scales(gcwt_plan* p, const float* dx, float* dout, int64_t ou
   HIP_TRY(hipMemcpy(sub->d_run_mask, mask.data(), (size_t)S, hipMemcpyHostToDevice));
   const int elem = hp.out_elem_bytes / (int)sizeof(float);
   const int64_t ch0 = channel >= 0 ? channel : 0;
-  float* dst = dout + (ch0 * S * row_len + (r0 - out_r0)) * elem;
+  float* dst = dout + (ch0 * S * row_len + stride_cols(out_r0, r0, p->out_stride)) * elem;
   sub->row_pitch = row_len;
   sub->run_mask = mask.data();
   const int rc = execute_range(sub, dx + ch0 * hp.prm.n_samples, dst, r0, r1, GCWT_X_ON_DEVICE | GCWT_OUT_ON_DEVICE);
@@ -1613,8 +1643,9 @@ static int execute_range(gcwt_plan* p, const void* x, void* out, int64_t r0, int
   if (rc) return rc;
   if (p->device >= 0) HIP_TRY(hipSetDevice(p->device));
   const HostPlan& hp = p->hp;
-  const int64_t n_out = r1 - r0;
+  const int64_t n_out = stride_cols(r0, r1, p->out_stride);   // output columns: the samples of [r0, r1) K divides
   const size_t rows = (size_t)hp.prm.n_channels * (size_t)hp.prm.n_freqs;
+  if (n_out == 0) return GCWT_OK;                              // a block range between two kept samples
   // host output: dense for the caller, padded to 32 samples on the device so that every
   // row starts on a 128-byte boundary; device output: the caller's pitch (0 = dense)
   int64_t row_len;

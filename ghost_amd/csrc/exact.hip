@@ -51,7 +51,9 @@ __global__ void __launch_bounds__(256) k_fullband_store(const cf* __restrict__ y
   const int64_t n = seg.w_lo[g] + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= seg.w_hi[g]) return;
   const cf v = y[(int64_t)c * p + n];
-  float* o = out + (((int64_t)ch * n_scales + scale) * row_len + seg.seg_col[g] + n) * kElem;
+  int64_t col = seg.seg_col[g] + n;
+  if (seg.os.k > 1 && !stride_keep(seg.os, seg.seg_col[g] + seg.os.r0 + n, &col)) return;   // output stride
+  float* o = out + (((int64_t)ch * n_scales + scale) * row_len + col) * kElem;
   if (MODE == GCWT_OUT_AMPLITUDE_F32) o[0] = sqrtf(v.x * v.x + v.y * v.y);
   else if (MODE == GCWT_OUT_POWER_F32) o[0] = v.x * v.x + v.y * v.y;
   else { o[0] = v.x; o[1] = v.y; }

@@ -58,11 +58,39 @@ struct SegIn {                       // forward column pass: where the segment's
   int64_t ramp_lo[kSegBatch], ramp_hi[kSegBatch];
   int32_t n_channels, pad;
 };
+// Output stride K (gcwt_plan_set_output_stride): recording sample n is stored only when K divides it, at column
+// n / K - c0 of its row (c0 = ceil(r0 / K), r0 the first sample of the call's range).  k = 1: every sample, at
+// column n - r0 -- the paths' own stores, untouched.
+struct OutStride {
+  int64_t r0 = 0;            // the call's first sample: segment-local sample s of segment g is n = seg_col[g] + r0 + s
+  int64_t c0 = 0;            // ceil(r0 / K)
+  int32_t k = 1;
+  uint32_t magic = 0;        // ceil(2^32 / K): n / K = umulhi(n, magic) for every multiple n of K below 2^32
+};
+inline OutStride make_out_stride(int64_t k, int64_t r0) {
+  OutStride o;
+  o.r0 = r0;
+  o.k = (int32_t)k;
+  o.c0 = (r0 + k - 1) / k;
+  o.magic = k > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)k - 1) / (uint64_t)k) : 0u;
+  return o;
+}
+// recording sample n (0 <= n < 2^31) is kept: *col = its column in the row.  For a multiple n of K,
+// n * ceil(2^32 / K) = n 2^32 / K + n e / K with e < K, so the high word is n / K exactly; any other n fails q K == n.
+__device__ __forceinline__ bool stride_keep(const OutStride& o, int64_t n, int64_t* col) {
+  const uint32_t t = (uint32_t)n;
+  const uint32_t q = __umulhi(t, o.magic);
+  *col = (int64_t)q - o.c0;
+  return n >= 0 && q * (uint32_t)o.k == t;
+}
+
 struct SegOut {                      // synthesis: where the segment's results go
   int64_t seg_col[kSegBatch];        // column of segment sample 0 in an out row (may be < 0)
   int64_t w_lo[kSegBatch];           // segment-local samples [w_lo, w_hi) are written
   int64_t w_hi[kSegBatch];
   int32_t n_channels, pad;
+  OutStride os;                      // k > 1: only the kept samples are written, at their strided columns
+                                     //   (the strided kernels, synths.hip; the store epilogues of the other paths)
 };
 
 struct SynthItemDev {
@@ -135,6 +163,9 @@ struct Synth7Args {
 // wide_halo: the items' levels have block halos above 48 (k_synth7<.., WIDE>); the other launch takes the rest
 hipError_t launch_synth7(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items, int n_channels,
                          hipStream_t st);
+// the same work with an output stride a.seg.os.k > 1 (synths.hip): every sample is made as k_synth7 makes it, only
+// the kept ones are stored
+hipError_t launch_synth7s(int mode, int ncol, const Synth7Args& a, int n_items, int n_channels, hipStream_t st);
 
 // Interpolating synthesis (synthi.hip): one workgroup = one block of one level, all its scales.
 struct SynthiItem {
@@ -171,6 +202,8 @@ struct SynthiArgs {
   SegOut seg;
 };
 hipError_t launch_synthi(int mode, const SynthiArgs& a, int n_items, int n_channels, hipStream_t st);
+// ... with an output stride a.seg.os.k > 1 (synths.hip): the interpolator runs only where a lane has a kept sample
+hipError_t launch_synthis(int mode, const SynthiArgs& a, int n_items, int n_channels, hipStream_t st);
 // Pipelined interpolating synthesis (synthp.hip): q = 2 levels with I = R / 2 <= 256; producer waves make the z of
 // round n + 1 while consumer waves interpolate and store round n.
 constexpr int kSynthpThreads = 512;
@@ -377,7 +410,8 @@ hipError_t launch_direct(int mode, const float* x, float* out, const float2* psi
                          const DirectScale* sc, int n_direct, const double* sums, double inv_n,
                          int64_t n_samples, int n_scales, const DirectEpochs& eps, int n_epochs,
                          int64_t col0, int64_t row_len, int64_t max_len, const float2* tail, hipStream_t st,
-                         const unsigned char* mask = nullptr);   // mask[scale row]: 0 = leave the row alone
+                         const unsigned char* mask = nullptr,    // mask[scale row]: 0 = leave the row alone
+                         const OutStride& os = OutStride());     // k > 1: the kept samples only (col0 = os.r0)
 // Block convolution (overlap-save; kernels.hip: k_bc_scales and fwd64.hip: k_bc_forward describe the path): the blocks of up to kSegBatch epochs that
 // one launch handles.  Blocks are `hop` samples long and aligned to multiples of `hop` in recording time; block
 // q of an epoch produces samples [q hop, (q + 1) hop) cut to [g_lo, g_hi) from the 4096 recording samples that
@@ -402,7 +436,7 @@ hipError_t launch_bc_forward(const float* x, float2* xb, const BcBlocks& bl, int
 hipError_t launch_bc_scales(int mode, const float2* xb, float* out, const float2* h, const int32_t* rows,
                             int n_group_scales, const float2* twt, const float2* tw256, const BcBlocks& bl,
                             int blk0, int nblk, int n_scales, int64_t col0, int64_t row_len, hipStream_t st,
-                            const unsigned char* mask = nullptr);
+                            const unsigned char* mask = nullptr, const OutStride& os = OutStride());
 hipError_t launch_level_small(const float2* x, float2* xr, int n1, int q, int64_t p1_stride,
                               int64_t x_cstride, int64_t xr_cstride, const float2* tw4096,
                               int n_channels, hipStream_t st, RowTaper taper = RowTaper());

@@ -898,13 +898,17 @@ struct Fullband4Set {
 struct FullbandSink {
   float* out;                 // the slot's channel, the scale's row, column of segment sample 0
   int64_t w_lo, w_hi;
+  OutStride os;               // k > 1: out is the row's column 0, n goes to its strided column (seg_col = n_seg - r0)
+  int64_t n_seg;
 };
 
 __device__ __forceinline__ FullbandSink fullband_sink(float* out, int slot, int scale, int n_scales,
                                                       int64_t row_len, const SegOut& seg, int elem) {
   const int g = slot / seg.n_channels, ch = slot - g * seg.n_channels;
   FullbandSink k;
-  k.out = out + (((int64_t)ch * n_scales + scale) * row_len + seg.seg_col[g]) * elem;
+  k.os = seg.os;
+  k.n_seg = seg.seg_col[g] + seg.os.r0;
+  k.out = out + (((int64_t)ch * n_scales + scale) * row_len + (seg.os.k > 1 ? 0 : seg.seg_col[g])) * elem;
   k.w_lo = seg.w_lo[g];
   k.w_hi = seg.w_hi[g];
   return k;
@@ -913,6 +917,7 @@ __device__ __forceinline__ FullbandSink fullband_sink(float* out, int slot, int 
 template <int MODE>
 __device__ __forceinline__ void fullband_put(const FullbandSink& k, int64_t n, cf v) {
   if (n < k.w_lo || n >= k.w_hi) return;
+  if (k.os.k > 1 && !stride_keep(k.os, k.n_seg + n, &n)) return;
   if (MODE == GCWT_OUT_AMPLITUDE_F32) k.out[n] = sqrtf(v.x * v.x + v.y * v.y);
   else if (MODE == GCWT_OUT_POWER_F32) k.out[n] = v.x * v.x + v.y * v.y;
   else reinterpret_cast<cf*>(k.out)[n] = v;
@@ -1111,7 +1116,7 @@ __global__ void __launch_bounds__(256, 2) k_bc_scales(const cf* __restrict__ xb,
                                                    int n_group_scales, const cf* __restrict__ twt,
                                                    const cf* __restrict__ tw256, const BcBlocks bl, int blk0,
                                                    int n_scales, int64_t col0, int64_t row_len,
-                                                   const unsigned char* __restrict__ mask) {
+                                                   const unsigned char* __restrict__ mask, const OutStride os) {
   // twt[256 j + tid] = W_4096^(+(t + 16 j) a): the middle twiddles in the order the threads meet them
   constexpr int kElem = MODE == GCWT_OUT_COMPLEX_C64 ? 2 : 1;
   __shared__ __attribute__((aligned(16))) cf buf[16 * kExColD];
@@ -1178,6 +1183,19 @@ __global__ void __launch_bounds__(256, 2) k_bc_scales(const cf* __restrict__ xb,
     for (int aa = 0; aa < 16; ++aa) v[aa] = bufv[kElemPitch * tid + aa];
     idft16v(v);
     float* const o = o0 + (int64_t)rows[s] * row_len * kElem;
+    if (os.k > 1) {                       // output stride: sample n0 - back + tid + 256 ka to its column, if kept
+      float* const orow = out + ((int64_t)ch * n_scales + rows[s]) * row_len * kElem;
+#pragma unroll
+      for (int ka = 0; ka < 16; ++ka) {
+        int64_t col;
+        if (256 * ka < first || 256 * ka >= last || !stride_keep(os, n0 - bl.back + tid + 256 * ka, &col)) continue;
+        const v2f w = v[dft16_pos(ka)];
+        if (MODE == GCWT_OUT_AMPLITUDE_F32) orow[col] = __builtin_amdgcn_sqrtf(w.x * w.x + w.y * w.y);
+        else if (MODE == GCWT_OUT_POWER_F32) orow[col] = w.x * w.x + w.y * w.y;
+        else reinterpret_cast<v2f*>(orow)[col] = w;
+      }
+      continue;
+    }
 #pragma unroll
     for (int ka = 0; ka < 16; ++ka) {
       if (256 * ka < first || 256 * ka >= last) continue;
@@ -1407,7 +1425,9 @@ __global__ void __launch_bounds__(256) k_synth(const SynthArgs a) {
 
   const cf* xb = a.xb + (int64_t)c * a.xb_cstride + lv.xb_offset;
   const cf* ltw = a.level_tw + lv.tw_offset;
-  float* out = a.out + (((int64_t)ch * a.n_scales + it.scale) * a.row_len + a.seg.seg_col[seg]) * kElem;
+  const bool strided = a.seg.os.k > 1;
+  const int64_t n_seg = a.seg.seg_col[seg] + a.seg.os.r0;          // recording sample of segment sample 0
+  float* out = a.out + (((int64_t)ch * a.n_scales + it.scale) * a.row_len + (strided ? 0 : a.seg.seg_col[seg])) * kElem;
 
   const int ncols = it.nblk * R;
   // per batch geometry of the staged tile
@@ -1469,8 +1489,8 @@ __global__ void __launch_bounds__(256) k_synth(const SynthArgs a) {
         count = hop * 16;
       }
       for (int q = threadIdx.x; q < count; q += 256) {
-        const int64_t n = n0 + (int64_t)(q >> 4) * row_stride + (q & 15);
-        if (n >= w_lo && n < w_hi) {
+        int64_t n = n0 + (int64_t)(q >> 4) * row_stride + (q & 15);
+        if (n >= w_lo && n < w_hi && (!strided || stride_keep(a.seg.os, n_seg + n, &n))) {
           if (kElem == 1) out[n] = tile[q];
           else { out[2 * n] = tile[2 * q]; out[2 * n + 1] = tile[2 * q + 1]; }
         }
@@ -1547,7 +1567,7 @@ __global__ void __launch_bounds__(256) k_direct(const float* __restrict__ x, flo
                                                 int64_t n_samples, int n_scales,
                                                 const DirectEpochs eps, int64_t col0,
                                                 int64_t row_len, int halo, const cf* __restrict__ tail,
-                                                const unsigned char* __restrict__ mask) {
+                                                const unsigned char* __restrict__ mask, const OutStride os) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int kElem = MODE == GCWT_OUT_COMPLEX_C64 ? 2 : 1;
   constexpr int kStageWave = 512 * kElem + 32 * kElem;        // floats of one wave's transposition area
@@ -1629,7 +1649,15 @@ __global__ void __launch_bounds__(256) k_direct(const float* __restrict__ x, flo
     __builtin_amdgcn_wave_barrier();
     float* const o_row = out + (((int64_t)c * n_scales + p.scale) * row_len + (g0 - col0) + 512 * wave) * kElem;
     const bool aligned = (reinterpret_cast<uintptr_t>(o_row) & 15) == 0;     // wave-uniform
-    if (aligned) {
+    if (os.k > 1) {                        // output stride (workgroup-uniform): the kept samples of the wave's 512
+      float* const s_row = out + ((int64_t)c * n_scales + p.scale) * row_len * kElem;
+      for (int f = lane; f * kElem < wave_left && f < 512; f += 64) {
+        int64_t col;
+        if (!stride_keep(os, g0 + 512 * wave + f, &col)) continue;
+#pragma unroll
+        for (int i = 0; i < kElem; ++i) s_row[col * kElem + i] = stage[direct_stage(f * kElem + i)];
+      }
+    } else if (aligned) {
 #pragma unroll
       for (int i = 0; i < 2 * kElem; ++i) {
         const int f = 256 * i + 4 * lane;
@@ -2082,7 +2110,7 @@ hipError_t launch_fullband_cols(int mode, const cf* z, float* out, int p1, int64
 hipError_t launch_bc_scales(int mode, const cf* xb, float* out, const cf* h, const int32_t* rows,
                             int n_group_scales, const cf* twt, const cf* tw256, const BcBlocks& bl, int blk0,
                             int nblk, int n_scales, int64_t col0, int64_t row_len, hipStream_t st,
-                            const unsigned char* mask) {
+                            const unsigned char* mask, const OutStride& os) {
   if (nblk <= 0 || n_group_scales <= 0) return hipSuccess;
   if (bl.n_epochs < 1 || bl.n_epochs > kSegBatch || bl.hop < 1 || bl.back < 0 || bl.hop + bl.back > kRowLenDev ||
       blk0 < 0 || blk0 + nblk > bl.blk_first[bl.n_epochs] || (int64_t)nblk * bl.n_channels > 0x7fffffff)
@@ -2090,7 +2118,7 @@ hipError_t launch_bc_scales(int mode, const cf* xb, float* out, const cf* h, con
   const dim3 grid((unsigned)(nblk * bl.n_channels)), block(256);
 #define GCWT_BC(M)                                                                                        \
   hipLaunchKernelGGL((k_bc_scales<M>), grid, block, 0, st, xb, out, h, rows, n_group_scales, twt, tw256, \
-                     bl, blk0, n_scales, col0, row_len, mask)
+                     bl, blk0, n_scales, col0, row_len, mask, os)
   if (mode == GCWT_OUT_AMPLITUDE_F32) GCWT_BC(GCWT_OUT_AMPLITUDE_F32);
   else if (mode == GCWT_OUT_POWER_F32) GCWT_BC(GCWT_OUT_POWER_F32);
   else GCWT_BC(GCWT_OUT_COMPLEX_C64);
@@ -2125,7 +2153,7 @@ hipError_t launch_direct(int mode, const float* x, float* out, const cf* psi, co
                          int n_direct, const double* sums, double inv_n, int64_t n_samples,
                          int n_scales, const DirectEpochs& eps, int n_epochs, int64_t col0,
                          int64_t row_len, int64_t max_len, const cf* tail, hipStream_t st,
-                         const unsigned char* mask) {
+                         const unsigned char* mask, const OutStride& os) {
   int64_t longest = 0;
   for (int e = 0; e < n_epochs; ++e) longest = std::max(longest, eps.g_hi[e] - eps.g_lo[e]);
   if (n_direct == 0 || n_epochs == 0 || longest <= 0) return hipSuccess;
@@ -2138,7 +2166,7 @@ hipError_t launch_direct(int mode, const float* x, float* out, const cf* psi, co
   dim3 grid((unsigned)((longest + kDirectTile - 1) / kDirectTile), 1, eps.n_channels * n_epochs), block(256);
 #define GCWT_DIRECT(M)                                                                       \
   hipLaunchKernelGGL((k_direct<M>), grid, block, lds, st, x, out, psi, sc, n_direct, sums,   \
-                     inv_n, n_samples, n_scales, eps, col0, row_len, halo, tail, mask)
+                     inv_n, n_samples, n_scales, eps, col0, row_len, halo, tail, mask, os)
   if (mode == GCWT_OUT_AMPLITUDE_F32) GCWT_DIRECT(GCWT_OUT_AMPLITUDE_F32);
   else if (mode == GCWT_OUT_POWER_F32) GCWT_DIRECT(GCWT_OUT_POWER_F32);
   else GCWT_DIRECT(GCWT_OUT_COMPLEX_C64);

@@ -138,15 +138,33 @@ _OUT_MODES = {"amplitude": _lib.OUT_AMPLITUDE, "power": _lib.OUT_POWER,
               "complex": _lib.OUT_COMPLEX}
 
 
+def output_stride_value(stride):
+    """The output stride K as an int: an integer >= 1 (numpy integers too); anything else -- bool, a float, K < 1 --
+    raises ValueError."""
+    if isinstance(stride, (bool, np.bool_)) or not isinstance(stride, (int, np.integer)):
+        raise ValueError("output_stride must be an integer >= 1, not %r" % (stride,))
+    if int(stride) < 1:
+        raise ValueError("output_stride must be an integer >= 1, not %d" % int(stride))
+    return int(stride)
+
+
+def stride_columns(start, stop, stride):
+    """Output columns of the samples [start, stop): the multiples of ``stride`` among them."""
+    return max(0, -(-int(stop) // stride) - -(-int(start) // stride))
+
+
 class CwtPlan:
     """One (n_channels, n_samples, frequencies, epochs) transform layout.
 
     Parameters mirror ``gcwt_params``; ``freqs_hz`` are the Morse peak
-    frequencies in the order the output rows are wanted."""
+    frequencies in the order the output rows are wanted.  ``output_stride`` K: row column j holds
+    sample K j (gcwt_plan_set_output_stride), ceil(N / K) columns."""
 
     def __init__(self, n_samples, n_channels, fs, freqs_hz, *, gamma=3.0, beta=20.0,
                  epoch_bounds=None, output="amplitude", device=-1, band_eps=0.0, block=0,
-                 max_fft_log2=0, normalization=None, order=0, precision=None, support_tol=0.0):
+                 max_fft_log2=0, normalization=None, order=0, precision=None, support_tol=0.0,
+                 output_stride=1):
+        stride = output_stride_value(output_stride)
         self._handle = C.c_void_p()
         self.freqs = np.ascontiguousarray(freqs_hz, dtype=np.float64)
         if epoch_bounds is None:
@@ -183,9 +201,13 @@ class CwtPlan:
         p.precision = {None: 0, "default": 0, "auto": 4, "fast": 1, "high": 2, "exact": 3}[precision]
         p.support_tol = float(support_tol)
         check(lib.gcwt_plan_create(C.byref(self._handle), C.byref(p)))
+        if stride != 1:
+            check(lib.gcwt_plan_set_output_stride(self._handle, stride))
         self.n_samples, self.n_channels = int(n_samples), int(n_channels)
         self.n_freqs = int(self.freqs.size)
-        self.out_shape = (self.n_channels, self.n_freqs, self.n_samples)
+        self.output_stride = stride
+        self.n_cols = stride_columns(0, self.n_samples, stride)     # output columns per row
+        self.out_shape = (self.n_channels, self.n_freqs, self.n_cols)
         self.out_dtype = _OUT_DTYPE[self.out_mode]
 
     # -- description ------------------------------------------------------
@@ -284,7 +306,7 @@ class CwtPlan:
         when it is one of this shape).  Rows are padded to 32 samples (128-byte row starts: DESIGN.md 5)."""
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_channels, self.n_samples)
         self.upload()                           # (without a GPU this is where GCWT_ERR_NO_DEVICE is raised)
-        pitch = (self.n_samples + 31) & ~31
+        pitch = (self.n_cols + 31) & ~31
         cplx = self.out_dtype == np.complex64
         if (result is None or result.buffer is None or result.shape != self.out_shape or result.pitch != pitch
                 or result.is_complex != cplx):
@@ -316,9 +338,11 @@ class CwtPlan:
 
     def execute_block(self, x, start, length, reuse_means=False, wide=False):
         """Samples [start, start+length) of every channel and scale from the whole
-        recording x (C, N): ndarray (C, S, length).  Host in, host out."""
+        recording x (C, N): ndarray (C, S, length) -- with an output stride, (C, S, columns): the samples of the
+        range that the stride divides.  Host in, host out."""
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_channels, self.n_samples)
-        out, flags = self._host_result((self.n_channels, self.n_freqs, int(length)), wide)
+        cols = stride_columns(start, int(start) + int(length), self.output_stride)
+        out, flags = self._host_result((self.n_channels, self.n_freqs, cols), wide)
         check(lib.gcwt_execute_block(self._handle, x.ctypes.data_as(C.c_void_p),
                                      out.ctypes.data_as(C.c_void_p), int(start), int(length),
                                      flags | (_lib.REUSE_MEANS if reuse_means else 0)))

@@ -100,7 +100,9 @@ class ShardedPlan:
             raise
         self.n_freqs = self.plans[0].n_freqs
         self.out_dtype = self.plans[0].out_dtype
-        self.out_shape = (self.n_channels, self.n_freqs, self.n_samples)
+        self.output_stride = self.plans[0].output_stride      # (output_stride=K reaches every plan through **kw)
+        self.n_cols = self.plans[0].n_cols
+        self.out_shape = (self.n_channels, self.n_freqs, self.n_cols)
         self.info = dict(self.plans[0].info)
         self.info["workspace_bytes"] = sum(p.info["workspace_bytes"] for p in self.plans)
         self.info["out_bytes"] = sum(p.info["out_bytes"] for p in self.plans)

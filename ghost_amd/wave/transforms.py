@@ -49,6 +49,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         self._power = None
         self._coefficients = None
         self._time = None
+        self._time_stride = 1               # output_stride of the last transform: time is timestamps[::K]
         self._plan = None
         self._plan_key = None
         self.last_timings = None
@@ -75,7 +76,11 @@ class ContinuousWaveletTransform(WaveletTransform):
         arithmetic, transforms.py:142-143, and the scales a mains line or the like inside their decimation band
         would cost more than 1.5e-6 of their peak are recomputed by exact FFT convolution, logged; 'high': the same
         without the recomputation, it only warns; 'fast': float32 throughout; 'exact': every scale by FFT
-        convolution with its literal kernel, 3 - 9 x slower).
+        convolution with its literal kernel, 3 - 9 x slower), ``output_stride`` (an integer K >= 1, default 1: only
+        every K-th sample of the recording's own grid is computed and kept -- column j holds sample K j, ceil(N / K)
+        columns, exactly the full-rate result's ``[..., ::K]``, gaps between epochs 0 as always; ``time`` is
+        ``timestamps[::K]`` and ``amplitude`` / ``power`` / ``coefficients`` / ``fetch()`` count columns.  Point
+        sampling: no average over the K samples).
         """
         if multichannel is None:
             multichannel = False
@@ -100,9 +105,12 @@ class ContinuousWaveletTransform(WaveletTransform):
 
     def _run(self, data, *, squeeze, timestamps=None, fs=None, freq_limits=None, freqs=None,
              voices_per_octave=None, parallel=None, verbose=None, output=None, dtype=None,
-             device=None, devices=None, precision=None, lazy=None, **kwargs):
+             device=None, devices=None, precision=None, lazy=None, output_stride=None, **kwargs):
+        from ..engine import output_stride_value
+        stride = output_stride_value(1 if output_stride is None else output_stride)   # before anything else
         self.fs = fs                        # validates (transforms.py:109)
         self._time = timestamps
+        self._time_stride = stride
 
         if freqs is not None and freq_limits is not None:
             raise ValueError("freq_limits and freqs cannot both be used at the"
@@ -193,7 +201,7 @@ class ContinuousWaveletTransform(WaveletTransform):
                              "its own filter lets through)")
         key = (n_samples, n_channels, float(self._fs), f.tobytes(), float(self._wavelet.gamma),
                float(self._wavelet.beta), epoch_bounds.tobytes(), output, int(device), precision,
-               None if devices is None else tuple(devices))
+               None if devices is None else tuple(devices), stride)
         if self._plan is None or self._plan_key != key:
             if self._plan is not None:
                 self._plan.close()
@@ -202,12 +210,12 @@ class ContinuousWaveletTransform(WaveletTransform):
                 from ..multi import ShardedPlan
                 self._plan = ShardedPlan(n_samples, n_channels, self._fs, f, devices, gamma=self._wavelet.gamma,
                                          beta=self._wavelet.beta, epoch_bounds=epoch_bounds,
-                                         output=output, precision=precision)
+                                         output=output, precision=precision, output_stride=stride)
             else:
                 self._plan = CwtPlan(n_samples, n_channels, self._fs, f, gamma=self._wavelet.gamma,
                                      beta=self._wavelet.beta, epoch_bounds=epoch_bounds,
                                      output=output, device=device if devices is None else devices[0],
-                                     precision=precision)
+                                     precision=precision, output_stride=stride)
             self._plan_key = key
         self._plan.set_profiling(bool(verbose))
         start_time = time.time()
@@ -282,7 +290,8 @@ class ContinuousWaveletTransform(WaveletTransform):
         return self._device_result
 
     def fetch(self, scales=None, start=0, stop=None, dtype=None):
-        """Scales ``scales`` (a slice; None = all) and samples [start, stop) of the last transform, straight from
+        """Scales ``scales`` (a slice; None = all) and columns [start, stop) of the last transform (samples; with an
+        output stride K, column j is sample K j), straight from
         the device, without bringing the rest of the result over: ndarray (S', n) -- (C, S', n) for multichannel
         transforms -- of what ``output=`` selected.  dtype: float32 or float64 (default: the transform's)."""
         if self._device_result is None:
@@ -474,6 +483,9 @@ class ContinuousWaveletTransform(WaveletTransform):
     def time(self):
         if isinstance(self._time, pre.RegularGrid):        # made by the adapter, not asked for until now
             self._time = np.asarray(self._time)
+        if self._time_stride > 1 and self._time is not None:   # output_stride: the kept samples' times
+            self._time = np.asarray(self._time)[::self._time_stride]
+            self._time_stride = 1
         return self._time
 
     @time.setter

@@ -236,6 +236,17 @@ int gcwt_plan_precision_report(const gcwt_plan* plan, float* predicted, float* w
  * cache lines; pad rows to a multiple of 32 samples for full speed when N is not one.
  * Host output buffers are always dense (the library pads internally). */
 int gcwt_plan_set_row_pitch(gcwt_plan* plan, int64_t pitch_samples);
+/* Output stride K >= 1 (1 = every sample, the default): output column j of a row holds the coefficient at sample
+ * n = K j of the recording's own grid (not per epoch), the full-rate result's [..., ::K] -- point sampling, no
+ * averaging.  Rows have ceil(N / K) columns: gcwt_plan_info.out_bytes, gcwt_execute's out and the row pitch of
+ * gcwt_plan_set_row_pitch count columns, and gcwt_execute_block(start, length) writes the kept samples of
+ * [start, start + length), the multiples of K there (any start), as that many columns.  Only the kept samples are
+ * stored.  Of the work: the interpolating synthesis (R >= 16) evaluates its FIR and |.| at the kept samples only; the
+ * 256-point synthesis skips the block phases that hold no kept sample when 4 divides K (one phase of R left when R
+ * divides K) and computes every phase otherwise; the other paths compute every sample and store the kept ones.
+ * Allowed from plan creation up to the first upload or execute; GCWT_ERR_INVALID after that or for K < 1;
+ * GCWT_ERR_UNSUPPORTED for K > 1 on recordings of 2^31 samples or more. */
+int gcwt_plan_set_output_stride(gcwt_plan* plan, int64_t stride);
 
 /* Device side ------------------------------------------------------------ */
 /* Allocate workspace, build the Morse filter bank and FFT tables on the
