@@ -50,6 +50,46 @@ def test_out_bytes_count_the_kept_columns(n, k, output):
     assert p.out_shape == (3, 4, cols)
 
 
+def _stride_keep(n, k):
+    """kernels.h: stride_keep in 32-bit arithmetic, for recording samples n (uint64, below 2^31): q = umulhi(n,
+    ceil(2^32 / K)) and whether q K == n (mod 2^32)."""
+    magic = np.uint64(((1 << 32) + int(k) - 1) // int(k))
+    q = (n * magic) >> np.uint64(32)
+    return ((q * np.uint64(k)) & np.uint64(0xFFFFFFFF)) == n, q
+
+
+LARGE_STRIDES = [4097, 5000, 65535, 65536, 65537, 99991, (1 << 17) + 1, 1000003, (1 << 20) - 1, 1 << 20]
+
+
+@pytest.mark.parametrize("ks", [range(2, 1025), range(1025, 4097), LARGE_STRIDES], ids=["2-1024", "1025-4096", "large"])
+def test_multiply_high_finds_the_column_of_every_multiple(ks):
+    """umulhi(n, ceil(2^32 / K)) == n // K for the multiples n of K below 2^31: the first and the last 512 of them and
+    1024 spread over the range (the product's error term n e / K, e < K, grows with n: the top is the tight end)."""
+    top = (1 << 31) - 1
+    for k in ks:
+        last = top // k
+        j = np.unique(np.concatenate([np.arange(0, min(512, last + 1)), np.arange(max(0, last - 511), last + 1),
+                                      np.linspace(0, last, 1024).astype(np.int64)])).astype(np.uint64)
+        n = j * np.uint64(k)
+        assert int(n.max()) <= top
+        kept, q = _stride_keep(n, k)
+        assert kept.all(), (k, n[~kept][:4])
+        np.testing.assert_array_equal(q, j, err_msg="K=%d" % k)
+
+
+@pytest.mark.parametrize("ks", [range(2, 1025), range(1025, 4097), LARGE_STRIDES], ids=["2-1024", "1025-4096", "large"])
+def test_multiply_high_rejects_every_other_sample(ks):
+    """The keep test (q K == n in 32 bits) holds for the multiples of K alone: every sample of windows of 4096 near 0
+    and near 2^31, and of K-sample runs spread in between."""
+    top = (1 << 31) - 1
+    for k in ks:
+        runs = [np.arange(s, s + k) for s in np.linspace(0, top - k, 9).astype(np.int64)]
+        n = np.unique(np.concatenate([np.arange(0, 4096), np.arange(top - 4095, top + 1)] + runs)).astype(np.uint64)
+        kept, q = _stride_keep(n, k)
+        np.testing.assert_array_equal(kept, n % np.uint64(k) == 0, err_msg="K=%d" % k)
+        np.testing.assert_array_equal(q[kept], n[kept] // np.uint64(k))
+
+
 def test_stride_may_change_until_the_plan_runs():
     """A plan created, its stride changed while nothing has run: the plan reports the new size each time."""
     from ghost_amd import _lib
