@@ -21,6 +21,7 @@
 #include "interp.h"
 #include "kernels.h"
 #include "morse_exact.h"
+#include "morlet_exact.h"
 #include "options.h"
 #include "planner.h"
 
@@ -694,10 +695,12 @@ static int gcwt_plan_upload_impl(gcwt_plan* p) {
     const ScalePlan& s = hp.scales[i];
     bsc[i] = {s.omega, s.half_delay, s.length, s.amp_offset, s.bin_lo, s.n_bins, s.decimation,
               s.method == GCWT_SCALE_SPECTRAL ? 1 : 0,
-              s.method == GCWT_SCALE_SPECTRAL ? hp.levels[s.level].band_shift : 0, 0};
+              s.method == GCWT_SCALE_SPECTRAL ? hp.levels[s.level].band_shift : 0, hp.morlet ? 1 : 0,
+              hp.morlet ? hp.prm.gamma : 0.0, s.sigma};
     if (s.method == GCWT_SCALE_DIRECT)
       dsc[s.direct_index] = {s.omega, s.length, s.amp_offset, s.direct_offset, i, s.bin_lo, s.n_bins,
-                              direct_front_pad(s.length)};
+                              direct_front_pad(s.length), hp.morlet ? 1 : 0, 0, hp.morlet ? hp.prm.gamma : 0.0,
+                              s.sigma, s.c0};
   }
   if ((rc = upload_vec(&p->d_bank_sc, bsc, p->stream))) return bail(rc);
   if ((rc = upload_vec(&p->d_direct_sc, dsc, p->stream))) return bail(rc);
@@ -734,26 +737,27 @@ static int gcwt_plan_upload_impl(gcwt_plan* p) {
   std::vector<float2> half_tw(hp.levels.size() * 256);
   for (size_t l = 0; l < hp.levels.size(); ++l) {
     scale_off[l] = (int)scale_list.size();
-    // odd kernel lengths (no half-sample delay, real filter) first, even ones after
+    // odd kernel lengths (no half-sample delay, real filter) first, even ones after; a Morlet scale's delay is in its
+    // complex row (k_gain_rows_complex), so all of them are "plain" and the half-sample ramp is never applied
     for (int sidx : hp.levels[l].scales)
-      if (hp.scales[sidx].half_delay == 0.0) scale_list.push_back(sidx);
+      if (hp.morlet || hp.scales[sidx].half_delay == 0.0) scale_list.push_back(sidx);
     n_plain[l] = (int)scale_list.size() - scale_off[l];
     for (int sidx : hp.levels[l].scales)
-      if (hp.scales[sidx].half_delay != 0.0) scale_list.push_back(sidx);
+      if (!hp.morlet && hp.scales[sidx].half_delay != 0.0) scale_list.push_back(sidx);
     for (int k = 0; k < 256; ++k) {
       const double a = -M_PI * (k - hp.levels[l].band_shift) / (256.0 * hp.levels[l].decimation);
       half_tw[l * 256 + k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
   }
   for (int sidx : scale_list)
-    scale_aux.push_back(hp.scales[sidx].demod_bin | (hp.scales[sidx].half_delay != 0.0 ? 1 << 16 : 0));
+    scale_aux.push_back(hp.scales[sidx].demod_bin | (!hp.morlet && hp.scales[sidx].half_delay != 0.0 ? 1 << 16 : 0));
   if ((rc = upload_vec(&p->d_half_tw, half_tw, p->stream))) return bail(rc);
   if ((rc = upload_vec(&p->d_scale_list, scale_list, p->stream))) return bail(rc);
   if ((rc = upload_vec(&p->d_scale_aux, scale_aux, p->stream))) return bail(rc);
   if ((rc = upload_vec(&p->d_interp_coef, hp.interp_coef, p->stream))) return bail(rc);
   p->n_listed = (int)scale_list.size();
   {   // k_synth7 reads whole chunks of 8 rows: 8 rows of zeros behind the last level's
-    const size_t n = ((size_t)p->n_listed + 8) * 256;
+    const size_t n = ((size_t)p->n_listed + 8) * 256 * (hp.morlet ? 2 : 1);     // (Morlet plans: complex rows)
     if ((rc = dev_alloc(&p->d_gain_lv, n))) return bail(rc);
     hipError_t hz = hipMemsetAsync(p->d_gain_lv, 0, sizeof(float) * n, p->stream);
     if (hz != hipSuccess) return bail(hip_err(hz, "gain rows reset"));
@@ -1004,6 +1008,10 @@ static int gcwt_plan_upload_impl(gcwt_plan* p) {
   he = launch_scale_windows(p->d_gain, p->d_scale_list, p->n_listed, (float)hp.band_tol, p->d_gain_lv,
                             p->prune_inputs, p->stream);
   if (he != hipSuccess) return bail(hip_err(he, "scale_windows"));
+  if (hp.morlet) {          // the rows k_synth7 reads are the bank's complex ones (the windows above are set from |H|)
+    he = launch_gain_rows_complex(p->d_bank, p->d_scale_list, p->n_listed, reinterpret_cast<float2*>(p->d_gain_lv), p->stream);
+    if (he != hipSuccess) return bail(hip_err(he, "gain_rows_complex"));
+  }
   he = launch_build_direct(p->d_psi, p->d_direct_sc, hp.n_direct, p->max_direct_len, p->d_amps, p->d_psi_tail,
                            p->d_psi_lit, p->stream);
   if (he != hipSuccess) return bail(hip_err(he, "build_direct"));
@@ -1390,6 +1398,7 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       a7.gain = p->d_gain;
       a7.gain_lv = p->d_gain_lv;
       a7.level_half_tw = p->d_half_tw;
+      a7.complex_gains = hp.morlet ? 1 : 0;
       a7.out = dout;
       a7.xb_cstride = hp.max_xb;
       a7.row_len = row_len;
@@ -2083,8 +2092,15 @@ int gcwt_debug_exact_gain(const gcwt_plan* p, int scale, const int64_t* a, int64
   if (!p || !a || !gain || b <= 0) return set_err(GCWT_ERR_INVALID, "bad argument");
   if (scale < 0 || scale >= (int)p->hp.scales.size()) return set_err(GCWT_ERR_INVALID, "scale out of range");
   const ScalePlan& s = p->hp.scales[scale];
-  for (int64_t i = 0; i < n; ++i)
+  for (int64_t i = 0; i < n; ++i) {
+    if (p->hp.morlet) {           // |H| of the closed form (its k = 0 term, real and positive, inside a scale's band)
+      double hr, hi;
+      morlet_response(p->hp.prm.gamma, s.sigma, s.half_delay, a[i], b, &hr, &hi);
+      gain[i] = std::sqrt(hr * hr + hi * hi);
+      continue;
+    }
     gain[i] = exact_gain(p->hp.amps.data() + s.amp_offset, s.bin_lo, s.n_bins, s.length, a[i], b);
+  }
   return GCWT_OK;
 }
 
@@ -2145,6 +2161,10 @@ int gcwt_internal_refresh_bank(gcwt_plan* p) {   // derived tables follow a (bro
   he = launch_scale_windows(p->d_gain, p->d_scale_list, p->n_listed, (float)p->hp.band_tol, p->d_gain_lv,
                             p->prune_inputs, p->stream);
   if (he != hipSuccess) return hip_err(he, "scale_windows");
+  if (p->hp.morlet) {
+    he = launch_gain_rows_complex(p->d_bank, p->d_scale_list, p->n_listed, reinterpret_cast<float2*>(p->d_gain_lv), p->stream);
+    if (he != hipSuccess) return hip_err(he, "gain_rows_complex");
+  }
   return GCWT_OK;
 }
 int gcwt_internal_set_error(int code, const char* msg) { return set_err(code, msg); }

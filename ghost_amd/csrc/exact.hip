@@ -11,6 +11,7 @@
 
 #include "kernels.h"
 #include "morse_exact.h"
+#include "morlet_exact.h"
 
 namespace gcwt {
 
@@ -24,6 +25,12 @@ __global__ void __launch_bounds__(256) k_fullband_filter(cf* __restrict__ h, con
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t k = (i >> 12) + (int64_t)p1 * (i & (kRowLenDev - 1));
   const int64_t P = (int64_t)p1 * kRowLenDev;
+  if (p.morlet) {       // the closed form on the whole grid, alias terms and the kernel's own delay included
+    double hr, hi;
+    morlet_response(p.w0, p.sigma, p.half_delay, k, P, &hr, &hi);
+    h[i] = make_float2((float)(hr / (double)P), (float)(hi / (double)P));
+    return;
+  }
   const double g = exact_gain(amps + p.amp_offset, p.bin_lo, p.n_bins, p.length, k, P) / (double)P;
   double sn, cs;
   sincospi(-2.0 * (double)k / (double)P * p.half_delay, &sn, &cs);

@@ -29,7 +29,10 @@ struct BankScale {
   int32_t decimation;
   int32_t spectral;
   int32_t band_shift;  // bank bin k is the frequency (k - band_shift) 2 pi / (256 R): the level's band starts
-  int32_t pad;         // that many bins below zero (planner.h: LevelPlan::band_shift)
+  int32_t morlet;      // that many bins below zero (planner.h: LevelPlan::band_shift)
+  // morlet != 0: no kept spectrum samples; the response is the closed form of morlet_exact.h for this w0 and sigma,
+  // half_delay the kernel's own delay d in (0, 1]
+  double w0, sigma;
 };
 
 struct DirectScale {
@@ -40,6 +43,9 @@ struct DirectScale {
   int32_t scale;        // output row
   int32_t bin_lo, n_bins;
   int32_t front;        // zero taps in front of the kernel in the psi buffer (direct_front_pad)
+  // morlet != 0: the taps are morlet_tap(w0, sigma, c0, n) (morlet_exact.h), not a sum over spectrum samples
+  int32_t morlet, pad;
+  double w0, sigma, c0;
 };
 
 // k_direct wants (L-1)/2 + front = 7 (mod 8): see the kernel's header
@@ -151,7 +157,8 @@ struct Synth7Args {
   const float2* xr;      // non-NULL: the workgroup computes its blocks' spectra itself from x_R
   int64_t xr_cstride;    //   (k_synth7 only; the block-spectra pass and the XB array are skipped)
   float xb_scale;        //   1 / (256 P)
-  int32_t pad0;
+  int32_t complex_gains; // Morlet plans: gain_lv holds complex rows H_s[k], [entry][t][16 j] float2 (k_gain_rows_complex),
+                         // and the launch takes the kernels' complex-gain instantiation
   unsigned long long* clock_probe;   // measure build only (GHOSTCWT_CLOCK_PROBE=1): [0] += shader cycles,
                                      // [1] += 100 MHz ticks each workgroup lived; NULL otherwise
   int32_t n_scales;
@@ -277,6 +284,8 @@ hipError_t launch_build_bank(float2* bank, float* gain, const BankScale* sc, con
 constexpr int kScaleIndexMask = 0x00FFFFFF;
 hipError_t launch_scale_windows(const float* gain, int32_t* scale_list, int n_listed, float tol,
                                 float* gain_lv, bool prune, hipStream_t st);
+hipError_t launch_gain_rows_complex(const float2* bank, const int32_t* scale_list, int n_listed, float2* gain_lv,
+                                    hipStream_t st);
 hipError_t launch_bank_gain(const float2* bank, float* gain, const BankScale* sc, int n_scales,
                             hipStream_t st);
 // full-band scales (exact.hip): H[k] / P on the k1-major grid of a P-point spectrum, the

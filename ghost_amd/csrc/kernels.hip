@@ -17,6 +17,7 @@
 
 #include "kernels.h"
 #include "morse_exact.h"
+#include "morlet_exact.h"
 #include "synth_math.h"
 
 namespace gcwt {
@@ -210,11 +211,21 @@ __global__ void k_build_bank(cf* __restrict__ bank, float* __restrict__ gain,
   if (p.spectral) {
     const int64_t b = (int64_t)B * p.decimation;
     const int kk = k - p.band_shift;         // bins are counted from the bottom of the level's band
+    if (p.morlet) {
+      // the closed form, delay and alias terms included (morlet_exact.h): one exponential per term instead of a
+      // sum over kept bins.  The row the synthesis reads is this complex H (k_gain_rows_complex); gain = |H|, which
+      // is H's k = 0 term -- real and positive -- wherever the level's band holds the scale
+      double hr, hi;
+      morlet_response(p.w0, p.sigma, p.half_delay, kk, b, &hr, &hi);
+      h = make_float2((float)hr, (float)hi);
+      g = (float)sqrt(hr * hr + hi * hi);
+    } else {
     const double gd = exact_gain(amps + p.amp_offset, p.bin_lo, p.n_bins, p.length, kk, b);
     double sn, cs;
     sincospi(-2.0 * (double)kk / (double)b * p.half_delay, &sn, &cs);
     h = make_float2((float)(gd * cs), (float)(gd * sn));
     g = (float)gd;
+    }
   }
   bank[(int64_t)s * B + k] = h;
   gain[(int64_t)s * B + k] = g;
@@ -229,9 +240,24 @@ __global__ void k_bank_gain(const cf* __restrict__ bank, float* __restrict__ gai
   const int s = blockIdx.x, k = threadIdx.x;
   const BankScale p = sc[s];
   const cf h = bank[(int64_t)s * 256 + k];
+  if (p.morlet) {                            // the rows the synthesis reads are the bank's own (k_gain_rows_complex)
+    gain[(int64_t)s * 256 + k] = sqrtf(h.x * h.x + h.y * h.y);
+    return;
+  }
   float sn, cs;
   sincospif((float)(2.0 * (double)(k - p.band_shift) / (256.0 * (double)p.decimation) * p.half_delay), &sn, &cs);
   gain[(int64_t)s * 256 + k] = h.x * cs - h.y * sn;
+}
+
+// Morlet plans: a scale's delay is its own, so its row for k_synth7 is the complex H_s[k] of the bank -- gain and
+// delay phase in one, made in float64 and rounded once (k_build_bank) -- laid out as k_scale_windows lays the real
+// rows: row = position in the level lists, lane t's sixteen values (bins t + 16 j) side by side.
+// grid (n_listed), block (256)
+__global__ void k_gain_rows_complex(const cf* __restrict__ bank, const int32_t* __restrict__ scale_list,
+                                    cf* __restrict__ gain_lv) {
+  const int k = threadIdx.x;
+  const int s = scale_list[blockIdx.x] & kScaleIndexMask;
+  gain_lv[(int64_t)blockIdx.x * 256 + (k & 15) * 16 + (k >> 4)] = bank[(int64_t)s * 256 + k];
 }
 
 // Which of the sixteen first-pass inputs of the synthesis (input j = bins 16 j .. 16 j + 15 of
@@ -291,7 +317,9 @@ __global__ void __launch_bounds__(256) k_build_direct(cf* __restrict__ psi, cons
   for (int64_t n0 = 0; n0 < L; n0 += 256) {
     const int64_t n = n0 + threadIdx.x;
     double re = 0.0, im = 0.0;
-    if (n < L) {
+    if (n < L && p.morlet) {
+      morlet_tap(p.w0, p.sigma, p.c0, n, &re, &im);        // get_wavelet()'s numbers (morlet.py:56-76)
+    } else if (n < L) {
       for (int32_t i = 0; i < p.n_bins; ++i) {
         const int64_t k = p.bin_lo + i;
         // phase = pi k (L+1)/L + 2 pi k n / L, reduced exactly: (k (L+1 + 2n)) mod 2L over L
@@ -1888,6 +1916,13 @@ hipError_t launch_scale_windows(const float* gain, int32_t* scale_list, int n_li
                      prune ? 1 : 0);
   GCWT_LAUNCH_CHECK();
   return hipSuccess;
+}
+
+hipError_t launch_gain_rows_complex(const cf* bank, const int32_t* scale_list, int n_listed, cf* gain_lv,
+                                    hipStream_t st) {
+  if (n_listed == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gain_rows_complex, dim3(n_listed), dim3(256), 0, st, bank, scale_list, gain_lv);
+  return hipGetLastError();
 }
 
 hipError_t launch_build_direct(cf* psi, const DirectScale* sc, int n_direct, int64_t max_len,

@@ -2,6 +2,7 @@
 #include "planner.h"
 #include "interp.h"
 #include "morse_exact.h"
+#include "morlet_exact.h"
 #include "options.h"
 
 #include <algorithm>
@@ -109,6 +110,50 @@ static void band_edges(double gamma, double beta, double eps, double* u_lo, doub
     if (morse_log_gain(mid, gamma, beta) < target) hi = mid; else lo = mid;
   }
   *u_hi = hi;
+}
+
+// The Morlet response in units of xi = sigma theta (morlet_exact.h: H is the shape F(xi) for every scale, stretched),
+// measured once per plan on the un-aliased shape:
+//  * xi_hi, xi_neg: outside [-xi_neg, xi_hi] |F| stays below band_tol of the peak.  Above the peak F falls
+//    monotonically.  Below zero F = -exp(-(xi - w0)^2 / 2) (exp(-w0 xi) - 1) has one extremum, exp(-w0^2 / 2) of the
+//    peak or so: under band_tol from w0 = 5.6 up (xi_neg = 0), above it for smaller w0, whose levels take a shifted band.
+//  * xi_lo: from zero frequency up, |F| stays below low_tol of the peak.
+//  * t_support: |psi|^2 is exp(-t^2 / sigma^2) to exp(-w0^2 / 2), so the energy beyond t_support sigma either side of the
+//    centre is erfc(t_support) of the whole: t_support solves erfc(t) = support_tol^2.
+// A scale with theta_hi + theta_neg <= pi has every alias term of H below band_tol inside its band as well.
+namespace {
+struct MorletBand { double xi_hi = 0, xi_neg = 0, xi_lo = 0, t_support = 0; };
+}  // namespace
+
+static MorletBand morlet_band(double w0, double band_tol, double low_tol, double support_tol) {
+  MorletBand mb;
+  double pk = 0.0, xi_pk = w0;
+  for (double xi = std::max(0.0, w0 - 2.0); xi <= w0 + 2.0; xi += 1e-4) {
+    const double f = morlet_shape(xi, w0);
+    if (f > pk) { pk = f; xi_pk = xi; }
+  }
+  auto bisect = [&](double in, double out, double lim) {      // |F(in)| > lim >= |F(out)|
+    for (int i = 0; i < 200; ++i) {
+      const double mid = 0.5 * (in + out);
+      if (std::fabs(morlet_shape(mid, w0)) > lim) in = mid; else out = mid;
+    }
+    return out;
+  };
+  mb.xi_hi = bisect(xi_pk, xi_pk + 60.0, band_tol * pk);
+  mb.xi_lo = std::min(xi_pk, bisect(xi_pk, 0.0, low_tol * pk));
+  double worst = 0.0, xi_worst = 0.0;
+  for (double xi = 0.0; xi >= -12.0; xi -= 1e-4) {
+    const double f = std::fabs(morlet_shape(xi, w0));
+    if (f > worst) { worst = f; xi_worst = xi; }
+  }
+  mb.xi_neg = worst > band_tol * pk ? -bisect(xi_worst, xi_worst - 60.0, band_tol * pk) : 0.0;
+  double lo = 0.0, hi = 30.0;
+  for (int i = 0; i < 200; ++i) {
+    const double mid = 0.5 * (lo + hi);
+    if (std::erfc(mid) > support_tol * support_tol) lo = mid; else hi = mid;
+  }
+  mb.t_support = hi;
+  return mb;
 }
 
 // Bins of the reference's L-point spectrum grid that matter: A_j above 1e-18 of the peak,
@@ -465,6 +510,9 @@ struct InterpDesign {
 }  // namespace
 
 static void plan_interp_level(HostPlan* hp, LevelPlan* lp, std::vector<float>* coef_out) {
+  // Morlet plans: the interpolator's polyphase tables hold the two delays of the Morse kernels (LevelPlan::coef_offset),
+  // not a delay per scale -- every level stays on the FFT-per-sample kernels
+  if (hp->morlet) { lp->interp_q = 0; return; }
   static std::mutex mu;
   static std::map<std::vector<double>, InterpDesign> cache;
   std::vector<double> key{(double)hp->block, (double)lp->decimation, (double)lp->band_shift, (double)hp->prm.out_mode,
@@ -521,9 +569,10 @@ int build_host_plan(const gcwt_params& prm, HostPlan* hp, std::string* err) {
   if (prm.n_freqs <= 0 || !prm.freqs_hz) return fail(GCWT_ERR_INVALID, "no analysis frequencies");
   if (!(prm.fs > 0) || !std::isfinite(prm.fs)) return fail(GCWT_ERR_INVALID, "Sampling rate must be positive and finite");
   if (!(prm.gamma > 0) || !std::isfinite(prm.gamma)) return fail(GCWT_ERR_INVALID, "gamma must be positive and finite");
-  if (!(prm.beta > 0) || !std::isfinite(prm.beta)) return fail(GCWT_ERR_INVALID, "beta must be positive and finite");
-  if (prm.wavelet_flags < 0 || (prm.wavelet_flags & ~(0xff | GCWT_WAVELET_ENERGY)) || (prm.wavelet_flags & 0xff) > 32)
-    return fail(GCWT_ERR_INVALID, "bad wavelet_flags (order 0..32, GCWT_WAVELET_ENERGY)");
+  const bool morlet = prm.wavelet_flags == GCWT_WAVELET_MORLET;      // gamma carries w0, beta is ignored
+  if (!morlet && (!(prm.beta > 0) || !std::isfinite(prm.beta))) return fail(GCWT_ERR_INVALID, "beta must be positive and finite");
+  if (!morlet && (prm.wavelet_flags < 0 || (prm.wavelet_flags & ~(0xff | GCWT_WAVELET_ENERGY)) || (prm.wavelet_flags & 0xff) > 32))
+    return fail(GCWT_ERR_INVALID, "bad wavelet_flags (order 0..32, GCWT_WAVELET_ENERGY; GCWT_WAVELET_MORLET on its own)");
   if (prm.out_mode < 0 || prm.out_mode > 2) return fail(GCWT_ERR_INVALID, "bad out_mode");
   if (prm.block != 0 && prm.block != 256)
     return fail(GCWT_ERR_UNSUPPORTED, "only block = 256 is built");
@@ -586,9 +635,16 @@ int build_host_plan(const gcwt_params& prm, HostPlan* hp, std::string* err) {
   }
 
   const double g = prm.gamma, b = prm.beta;
-  hp->w0 = std::exp((std::log(b) - std::log(g)) / g);                 // morseutils.py:315
-  hp->base_length = (2.0 * std::sqrt(2.0) * std::sqrt(g * b)) / hp->w0 * 4.0;  // morse.py:115
-  band_edges(g, b, 1e-18, &hp->u_lo, &hp->u_hi);
+  hp->morlet = morlet;
+  MorletBand mb;
+  if (morlet) {
+    hp->w0 = g;
+    mb = morlet_band(g, hp->band_tol, hp->low_tol, hp->support_tol);
+  } else {
+    hp->w0 = std::exp((std::log(b) - std::log(g)) / g);                 // morseutils.py:315
+    hp->base_length = (2.0 * std::sqrt(2.0) * std::sqrt(g * b)) / hp->w0 * 4.0;  // morse.py:115
+    band_edges(g, b, 1e-18, &hp->u_lo, &hp->u_hi);
+  }
 
   // Per scale: the reference's kernel length, its kept spectrum samples, and what the
   // exact response of that kernel allows (analyse_scale).  A scale is
@@ -610,6 +666,24 @@ int build_host_plan(const gcwt_params& prm, HostPlan* hp, std::string* err) {
     if (!(sp.freq_hz > 0) || !std::isfinite(sp.freq_hz)) return fail(GCWT_ERR_INVALID, "analysis frequencies must be positive and finite");
     if (sp.freq_hz > 0.5 * prm.fs) return fail(GCWT_ERR_INVALID, "analysis frequency above the Nyquist frequency fs / 2");
     sp.omega = sp.freq_hz / (prm.fs / 2.0) * M_PI;                    // transforms.py:408-410
+    if (morlet) {
+      // the kernel of morlet.py:56-76: its length, the scale in samples and the delay of its centre; the band and
+      // the support follow from the closed form, which is one function of sigma theta for every scale
+      const MorletScale ms = morlet_scale(g, sp.freq_hz, prm.fs);
+      if (!(ms.length <= ((int64_t)1 << 40))) return fail(GCWT_ERR_UNSUPPORTED, "kernel length beyond 2^40");
+      sp.length = ms.length;
+      sp.sigma = ms.sigma;
+      sp.c0 = ms.c0;
+      sp.half_delay = ms.delay;
+      sp.theta_hi = mb.xi_hi / ms.sigma;
+      sp.theta_neg = std::min(M_PI, mb.xi_neg / ms.sigma);
+      sp.theta_lo = mb.xi_neg > 0.0 ? 0.0 : mb.xi_lo / ms.sigma;
+      sp.band_ok = sp.theta_hi + sp.theta_neg <= M_PI;
+      // (the centre sits up to one sample off the 'same' origin; a kernel that answers down to zero frequency keeps
+      // its whole length under precision = high, as in analyse_scale)
+      sp.support = std::min(0.5 * (double)sp.length, mb.t_support * ms.sigma + 1.0);
+      if (hp->high_precision && !(sp.theta_lo > 0.0)) sp.support = 0.5 * (double)sp.length;
+    } else {
     sp.length = (int64_t)std::ceil(hp->w0 / sp.omega * hp->base_length);  // morse.py:118-122
     if (sp.length < 1) sp.length = 1;
     if (sp.length > ((int64_t)1 << 40)) return fail(GCWT_ERR_UNSUPPORTED, "kernel length beyond 2^40");
@@ -619,6 +693,7 @@ int build_host_plan(const gcwt_params& prm, HostPlan* hp, std::string* err) {
     hp->amps.insert(hp->amps.end(), amp.begin(), amp.end());
     hp->max_bins = std::max(hp->max_bins, (int)sp.n_bins);
     analyse_scale(*hp, &sp, amp.data());
+    }
     if (hp->exact_only) sp.band_ok = false;
     sp.method = sp.band_ok ? GCWT_SCALE_SPECTRAL
                            : exact_method(*hp, sp.length);

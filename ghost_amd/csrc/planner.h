@@ -42,7 +42,9 @@ struct ScalePlan {
   int method = GCWT_SCALE_SPECTRAL;
   int decimation = 1;              // R
   int level = -1;                  // index into HostPlan::levels
-  double half_delay = 0;           // d = (L-1)/2 - (L-1)//2
+  double half_delay = 0;           // d = (L-1)/2 - (L-1)//2; Morlet plans: the kernel's own delay c0 - (L-1)//2 in
+                                   // (0, 1] (morlet_exact.h)
+  double sigma = 0, c0 = 0;        // Morlet plans: the scale in samples and the array index of the wavelet's centre
   int direct_index = -1;           // index among direct scales
   int64_t direct_offset = 0;       // offset of psi in the direct-kernel buffer (complex elems)
   int fullband_index = -1;         // index among full-band scales
@@ -145,6 +147,8 @@ struct HostPlan {
   double low_tol = 2e-8;           // response below a scale's band a level's low cut may drop, relative to the peak
                                    // (the L-tap truncation's side lobes sit at 5e-9 .. 1e-8 there for the default wavelet)
   bool high_precision = true;      // gcwt_params.precision: float64 forward transform + per-level low cut
+  bool morlet = false;             // GCWT_WAVELET_MORLET: prm.gamma carries w0; no kept spectrum samples (amps is
+                                   // empty), every response comes from the closed form of morlet_exact.h
   double w0 = 0;                   // (beta/gamma)^(1/gamma)          (morseutils.py:315)
   double base_length = 0;          // 2 sqrt2 sqrt(gamma beta)/w0 * 4 (morse.py:115-116)
   double u_lo = 0, u_hi = 0;       // continuous spectrum above 1e-18 of its peak on [u_lo, u_hi] * omega

@@ -65,14 +65,20 @@ __device__ __forceinline__ void twiddle_to_planes(v2f* exw, const v2f (&v)[16], 
 // constant goes into its spectrum, the phase's into P, and the position's into the W256
 // twiddles and the order of the exchange planes (the same device as synthi.hip's
 // demodulation): nothing is added to the scale loop.
-template <int MODE, int NCOL, bool WIDE>
+// CG: the Morlet instantiation.  A Morlet kernel's delay against the 'same' origin is a real number of its own for
+// every scale (morlet_exact.h), which the one half-sample ramp of the level cannot carry: the scale's row is the
+// complex H_s[k] = G_s(theta_k) exp(-i theta_k d_s) (k_gain_rows_complex), parked as float2 and applied as a packed
+// complex multiply where the Morse instantiation applies a real scale; no half-sample case (n_plain = n_scales).
+template <int MODE, int NCOL, bool WIDE, bool CG = false>
 __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const Synth7Args a) {
   constexpr int kThreads = 16 * NCOL;
   constexpr int kPlane = kThreads + 1;
   constexpr int kLgN = NCOL == 32 ? 5 : 4;
   // gains of one scale in LDS: lane t's sixteen (bins t + 16 j) side by side, 20 floats per lane so
   // that the four 16-byte reads of the 16 lanes of a column fall on distinct banks
-  constexpr int kGainRow = 16 * 20;
+  // CG (complex rows): lane t's sixteen float2, 36 floats per lane -- eight 16-byte reads, the 16 lanes of a column on
+  // distinct banks again -- and four scales to a chunk, so that the staging area stays the 10 KB it is
+  constexpr int kGainRow = CG ? 16 * 36 : 16 * 20;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v2f* const ex = reinterpret_cast<v2f*>(smem);
   // W256 twiddles of the inter-stage multiply, lane t's sixteen side by side (pitch 18: 144 bytes, so
@@ -80,7 +86,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
   constexpr int kTwPitch = 18;
   v2f* const twl = ex + 16 * kPlane;
   float* const stage = reinterpret_cast<float*>(twl + 16 * kTwPitch);   // gains of kChunk scales
-  int* const sc_lds = reinterpret_cast<int*>(stage + 8 * kGainRow);   // this level's scale indices
+  int* const sc_lds = reinterpret_cast<int*>(stage + 8 * 320);   // this level's scale indices
   v2f* const half_lds = reinterpret_cast<v2f*>(sc_lds + 256);         // the level's half-sample factors
 
   const Synth7Item it = a.items[blockIdx.x];
@@ -104,7 +110,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
   const int blk_l = wide ? 0 : (colw >> lg);
   const int r = wide ? it.rtile * NCOL + colw : (colw & (R - 1));
   const int* const scales = a.scale_list + lv.scale_offset;
-  constexpr int kChunk = 8;
+  constexpr int kChunk = CG ? 4 : 8;
   // ---- every global load of the prologue is issued here, before anything waits for one: the
   // workgroup pays one trip to memory, not one per table ----
   // this level's scale entries (read from LDS inside the loop: a global load there would have to
@@ -118,19 +124,23 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
   // parked in LDS (10 KB), lane t's sixteen side by side; gain_lv holds them in that order
   // (k_scale_windows), one 16-byte load per thread and chunk, the next chunk's issued as soon as
   // the current one is parked.
-  constexpr int kGainLoads = kChunk * 64 / kThreads;     // float4 per thread and chunk: 1 (2 for 16 columns)
-  static_assert(kGainLoads * kThreads == kChunk * 64, "one chunk = a whole number of loads per thread");
-  const float4* const gain_rows = reinterpret_cast<const float4*>(a.gain_lv + (int64_t)lv.scale_offset * 256);
+  constexpr int kRowVec = CG ? 128 : 64;                 // float4 per scale's row
+  constexpr int kGainLoads = kChunk * kRowVec / kThreads;   // float4 per thread and chunk: 1 (2 for 16 columns)
+  static_assert(kGainLoads * kThreads == kChunk * kRowVec, "one chunk = a whole number of loads per thread");
+  const float4* const gain_rows = reinterpret_cast<const float4*>(a.gain_lv + (int64_t)lv.scale_offset * (4 * kRowVec));
   static_assert(kGainLoads == 1 || kGainLoads == 2, "one or two 16-byte loads per thread and chunk");
   // (two named registers, not an array: captured by the lambdas below an array of two went to scratch memory -- 48 bytes
   // of private segment per lane and a scratch set-up for every wave of the 16-column instantiation)
   float4 g_v0 = make_float4(0.f, 0.f, 0.f, 0.f), g_v1 = g_v0;
   auto load_gains = [&](int b0) {
-    g_v0 = gain_rows[b0 * 64 + tid];
-    if constexpr (kGainLoads > 1) g_v1 = gain_rows[b0 * 64 + kThreads + tid];
+    g_v0 = gain_rows[b0 * kRowVec + tid];
+    if constexpr (kGainLoads > 1) g_v1 = gain_rows[b0 * kRowVec + kThreads + tid];
   };
   auto park_one = [&](int f, const float4& g) {          // float4 f of the chunk: scale f >> 6, lane (f >> 2) & 15
-    *reinterpret_cast<float4*>(stage + (f >> 6) * kGainRow + ((f >> 2) & 15) * 20 + (f & 3) * 4) = g;
+    if constexpr (CG)                                    // ... scale f >> 7, lane (f >> 3) & 15
+      *reinterpret_cast<float4*>(stage + (f >> 7) * kGainRow + ((f >> 3) & 15) * 36 + (f & 7) * 4) = g;
+    else
+      *reinterpret_cast<float4*>(stage + (f >> 6) * kGainRow + ((f >> 2) & 15) * 20 + (f & 3) * 4) = g;
   };
   auto park_gains = [&]() {
     park_one(tid, g_v0);
@@ -285,7 +295,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
   const bool keep_p0 = upper ? keep2 : keep1, keep_p6 = upper ? keep14 : keep13;
   const unsigned voff_pair = voff0 - (upper ? (unsigned)((2 * hop - 32) * 4) : 0u);   // the wave's first block, lane-linear
   const unsigned pair_step = (unsigned)(2 * hop * 4);                              // its second block
-  const float* const st_rd = stage + t * 20;
+  const float* const st_rd = stage + t * (CG ? 36 : 20);
   __syncthreads();
   if (kMeasureBuild && a.clock_probe) probe_ph[3] = __builtin_amdgcn_s_memrealtime();
 
@@ -301,14 +311,15 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
       for (int j = 0; j < 16; ++j) pw[j] = cmulv(pw[j], half_lds[t + 16 * j]);
     }
     const float4* const hs = reinterpret_cast<const float4*>(st_rd + (b & (kChunk - 1)) * kGainRow);
+    [[maybe_unused]] const v4f* const hc = reinterpret_cast<const v4f*>(hs);
     // the entry's top byte: 16 - j_hi, first-pass inputs j >= j_hi are left out for this scale (kernels.h)
     const int entry = __builtin_amdgcn_readfirstlane(sc_lds[b]);
     v2f v[16];
     switch ((unsigned)entry >> 24) {             // wave-uniform; 16 - j_hi
-#define GCWT_WINDOW(hi) case 16 - (hi): gain_first_layer<hi>(v, pw, hs); break;
+#define GCWT_WINDOW(hi) case 16 - (hi): if constexpr (CG) gain_first_layer_c<hi>(v, pw, hc); else gain_first_layer<hi>(v, pw, hs); break;
       GCWT_WINDOW(15) GCWT_WINDOW(14) GCWT_WINDOW(13) GCWT_WINDOW(12) GCWT_WINDOW(11) GCWT_WINDOW(10) GCWT_WINDOW(9)
 #undef GCWT_WINDOW
-      default: gain_first_layer<16>(v, pw, hs); break;
+      default: if constexpr (CG) gain_first_layer_c<16>(v, pw, hc); else gain_first_layer<16>(v, pw, hs); break;
     }
     idft16v_tail(v);
     // the column's sixteen values, W256^(t j) applied, into its exchange planes: with the stride between
@@ -381,7 +392,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
   }
 }
 
-template <int NCOL, bool WIDE>
+template <int NCOL, bool WIDE, bool CG>
 static hipError_t launch_synth7_n(int mode, const Synth7Args& a, int n_items, int n_channels,
                                   hipStream_t st) {
   constexpr int lds = 16 * (16 * NCOL + 1) * 8 + 16 * 18 * 8 + 8 * 320 * 4 + 256 * 4 + 256 * 8;
@@ -390,35 +401,53 @@ static hipError_t launch_synth7_n(int mode, const Synth7Args& a, int n_items, in
   (void)hipGetDevice(&dev_);
   bool& attr_set = attr_done[dev_ & 63];
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_AMPLITUDE_F32, NCOL, WIDE>,
+    hipError_t e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_AMPLITUDE_F32, NCOL, WIDE, CG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_POWER_F32, NCOL, WIDE>,
+    e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_POWER_F32, NCOL, WIDE, CG>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_COMPLEX_C64, NCOL, WIDE>,
+    e = hipFuncSetAttribute((const void*)k_synth7<GCWT_OUT_COMPLEX_C64, NCOL, WIDE, CG>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
   dim3 grid(n_items, n_channels), block(16 * NCOL);
   if (mode == GCWT_OUT_AMPLITUDE_F32)
-    hipLaunchKernelGGL((k_synth7<GCWT_OUT_AMPLITUDE_F32, NCOL, WIDE>), grid, block, lds, st, a);
+    hipLaunchKernelGGL((k_synth7<GCWT_OUT_AMPLITUDE_F32, NCOL, WIDE, CG>), grid, block, lds, st, a);
   else if (mode == GCWT_OUT_POWER_F32)
-    hipLaunchKernelGGL((k_synth7<GCWT_OUT_POWER_F32, NCOL, WIDE>), grid, block, lds, st, a);
+    hipLaunchKernelGGL((k_synth7<GCWT_OUT_POWER_F32, NCOL, WIDE, CG>), grid, block, lds, st, a);
   else
-    hipLaunchKernelGGL((k_synth7<GCWT_OUT_COMPLEX_C64, NCOL, WIDE>), grid, block, lds, st, a);
+    hipLaunchKernelGGL((k_synth7<GCWT_OUT_COMPLEX_C64, NCOL, WIDE, CG>), grid, block, lds, st, a);
   return hipGetLastError();
 }
 
+template <bool CG>
+static hipError_t launch_synth7_cg(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items,
+                                   int n_channels, hipStream_t st) {
+  if (wide_halo)
+    return ncol == 16 ? launch_synth7_n<16, true, CG>(mode, a, n_items, n_channels, st)
+                      : launch_synth7_n<32, true, CG>(mode, a, n_items, n_channels, st);
+  return ncol == 16 ? launch_synth7_n<16, false, CG>(mode, a, n_items, n_channels, st)
+                    : launch_synth7_n<32, false, CG>(mode, a, n_items, n_channels, st);
+}
+
+// The complex-gain instantiations live in a code object of their own (synth_morlet.hip compiles this file with
+// GCWT_SYNTH_MORLET_TU), so that this one holds the kernels it always held, where it always held them.
+hipError_t launch_synth7_morlet(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items, int n_channels,
+                                hipStream_t st);
+#ifdef GCWT_SYNTH_MORLET_TU
+hipError_t launch_synth7_morlet(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items, int n_channels,
+                                hipStream_t st) {
+  return launch_synth7_cg<true>(mode, ncol, wide_halo, a, n_items, n_channels, st);
+}
+#else
 hipError_t launch_synth7(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items, int n_channels,
                          hipStream_t st) {
   if (n_items == 0) return hipSuccess;
-  if (wide_halo)
-    return ncol == 16 ? launch_synth7_n<16, true>(mode, a, n_items, n_channels, st)
-                      : launch_synth7_n<32, true>(mode, a, n_items, n_channels, st);
-  return ncol == 16 ? launch_synth7_n<16, false>(mode, a, n_items, n_channels, st)
-                    : launch_synth7_n<32, false>(mode, a, n_items, n_channels, st);
+  return a.complex_gains ? launch_synth7_morlet(mode, ncol, wide_halo, a, n_items, n_channels, st)
+                         : launch_synth7_cg<false>(mode, ncol, wide_halo, a, n_items, n_channels, st);
 }
+#endif
 
 }  // namespace gcwt

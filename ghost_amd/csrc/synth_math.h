@@ -82,6 +82,24 @@ __device__ __forceinline__ void gain_first_layer(v2f v[16], const v2f p[16], con
   bfly4_in<(11 >= JHI), (15 >= JHI)>(v[3], v[7], v[11], v[15]);
 }
 
+// The same with complex gains (Morlet plans: a scale's row is H_s[k] = G_s exp(-i theta_k d_s), the delay d_s its own):
+// a packed complex multiply where the real row takes a scale.  g: the lane's 16 gains as eight float4, two each.
+template <int JHI>
+__device__ __forceinline__ void gain_first_layer_c(v2f v[16], const v2f p[16], const v4f* g) {
+  static_assert(JHI >= 9 && JHI <= 16, "inputs 0..8 are always computed");
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    if (2 * q >= JHI) continue;
+    const v4f gq = g[q];
+    v[2 * q] = cmulv(p[2 * q], (v2f){gq.x, gq.y});
+    if (2 * q + 1 < JHI) v[2 * q + 1] = cmulv(p[2 * q + 1], (v2f){gq.z, gq.w});
+  }
+  bfly4_in<(8 >= JHI), (12 >= JHI)>(v[0], v[4], v[8], v[12]);
+  bfly4_in<(9 >= JHI), (13 >= JHI)>(v[1], v[5], v[9], v[13]);
+  bfly4_in<(10 >= JHI), (14 >= JHI)>(v[2], v[6], v[10], v[14]);
+  bfly4_in<(11 >= JHI), (15 >= JHI)>(v[3], v[7], v[11], v[15]);
+}
+
 // the rest of idft16v after its first layer: twiddles W16^(n1 k2), second radix-4 layer
 __device__ __forceinline__ void idft16v_tail(v2f v[16]) {
   const v2f w1 = {0.92387953251128674f, 0.38268343236508977f};   // W16^1

@@ -157,13 +157,14 @@ class CwtPlan:
     """One (n_channels, n_samples, frequencies, epochs) transform layout.
 
     Parameters mirror ``gcwt_params``; ``freqs_hz`` are the Morse peak
-    frequencies in the order the output rows are wanted.  ``output_stride`` K: row column j holds
+    frequencies in the order the output rows are wanted (``morlet_w0=w0``: the ``freq`` of
+    ``Morlet(w0, freq, fs)`` instead, and ``gamma`` / ``beta`` are ignored).  ``output_stride`` K: row column j holds
     sample K j (gcwt_plan_set_output_stride), ceil(N / K) columns."""
 
     def __init__(self, n_samples, n_channels, fs, freqs_hz, *, gamma=3.0, beta=20.0,
                  epoch_bounds=None, output="amplitude", device=-1, band_eps=0.0, block=0,
                  max_fft_log2=0, normalization=None, order=0, precision=None, support_tol=0.0,
-                 output_stride=1):
+                 output_stride=1, morlet_w0=None):
         stride = output_stride_value(output_stride)
         self._handle = C.c_void_p()
         self.freqs = np.ascontiguousarray(freqs_hz, dtype=np.float64)
@@ -193,6 +194,16 @@ class CwtPlan:
         if not 0 <= int(order) <= 32:
             raise ValueError("order must be between 0 and 32")
         p.wavelet_flags = int(order) | (_lib.WAVELET_ENERGY if normalization == "energy" else 0)
+        # morlet_w0: the Morlet wavelet of that non-dimensional frequency instead (GCWT_WAVELET_MORLET: gamma
+        # carries w0, beta is ignored, no order or normalisation); freqs_hz are its ``freq``
+        if morlet_w0 is not None:
+            if normalization is not None or int(order) != 0:
+                raise ValueError("a Morlet plan takes neither 'normalization' nor 'order'")
+            if not float(morlet_w0) > 0:
+                raise ValueError("Frequency ratio must be positive")
+            p.gamma = float(morlet_w0)
+            p.beta = 0.0
+            p.wavelet_flags = _lib.WAVELET_MORLET
         # 'auto' (default): float64 forward transform and per-level low cut, the reference's dynamic range (it
         # computes in float64: transforms.py:142-143), with the scales at risk recomputed exactly; 'high': the same
         # without the recomputation; 'fast': float32 throughout; 'exact': no decimated path

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import wavelet as wavedef
 from . import morse
+from . import morlet
 from ..formats import preprocessing as pre
 
 __all__ = ["ContinuousWaveletTransform"]
@@ -36,7 +37,10 @@ class ContinuousWaveletTransform(WaveletTransform):
     Parameters
     ----------
     wavelet : ghost_amd.Wavelet, optional
-        Default is ``Morse()`` (gamma=3, beta=20).
+        Default is ``Morse()`` (gamma=3, beta=20).  ``Morse(gamma, beta)`` or ``Morlet(w0)``: with a
+        Morlet wavelet row ``f`` is the convolution with ``Morlet(w0, f, fs).get_wavelet()``, the
+        frequency grid comes from ``Morlet.compute_freq_bounds`` and every keyword of ``transform()``
+        works as with a Morse one (``w0 < 5`` is not admissible but is computed as asked).
     """
 
     def __init__(self, *, wavelet=None):
@@ -199,8 +203,13 @@ class ContinuousWaveletTransform(WaveletTransform):
                              "reference's float64 dynamic range in front of the float32 synthesis), 'fast' (float32 "
                              "throughout) or 'exact' (no decimated path: every scale's float32 stages see only what "
                              "its own filter lets through)")
-        key = (n_samples, n_channels, float(self._fs), f.tobytes(), float(self._wavelet.gamma),
-               float(self._wavelet.beta), epoch_bounds.tobytes(), output, int(device), precision,
+        # the wavelet family and its parameters, as the plan key and as CwtPlan's keywords
+        if isinstance(self._wavelet, morlet.Morlet):
+            family = {"morlet_w0": float(self._wavelet.w0)}
+        else:
+            family = {"gamma": float(self._wavelet.gamma), "beta": float(self._wavelet.beta)}
+        key = (n_samples, n_channels, float(self._fs), f.tobytes(), tuple(sorted(family.items())),
+               epoch_bounds.tobytes(), output, int(device), precision,
                None if devices is None else tuple(devices), stride)
         if self._plan is None or self._plan_key != key:
             if self._plan is not None:
@@ -208,14 +217,12 @@ class ContinuousWaveletTransform(WaveletTransform):
                 self._plan = None
             if devices is not None and n_channels > 1:
                 from ..multi import ShardedPlan
-                self._plan = ShardedPlan(n_samples, n_channels, self._fs, f, devices, gamma=self._wavelet.gamma,
-                                         beta=self._wavelet.beta, epoch_bounds=epoch_bounds,
-                                         output=output, precision=precision, output_stride=stride)
+                self._plan = ShardedPlan(n_samples, n_channels, self._fs, f, devices, epoch_bounds=epoch_bounds,
+                                         output=output, precision=precision, output_stride=stride, **family)
             else:
-                self._plan = CwtPlan(n_samples, n_channels, self._fs, f, gamma=self._wavelet.gamma,
-                                     beta=self._wavelet.beta, epoch_bounds=epoch_bounds,
+                self._plan = CwtPlan(n_samples, n_channels, self._fs, f, epoch_bounds=epoch_bounds,
                                      output=output, device=device if devices is None else devices[0],
-                                     precision=precision, output_stride=stride)
+                                     precision=precision, output_stride=stride, **family)
             self._plan_key = key
         self._plan.set_profiling(bool(verbose))
         start_time = time.time()

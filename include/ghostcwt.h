@@ -108,6 +108,13 @@ typedef struct {
 } gcwt_params;
 
 #define GCWT_WAVELET_ENERGY 0x100
+/* Bit 9: the Morlet wavelet instead of a Morse one (morlet.py:56-76).  `gamma` then carries w0, the
+ * non-dimensional frequency (> 0; below 5 the wavelet is not admissible but is computed as asked), `beta`
+ * is ignored, and the order bits and GCWT_WAVELET_ENERGY must be 0 (else GCWT_ERR_INVALID).  freqs_hz are
+ * the frequencies `freq` of Morlet(w0, freq, fs); row f is the 'same'-mode convolution of the recording with
+ * Morlet(w0, freq, fs).get_wavelet(), as it is with the Morse kernel otherwise.  Morlet plans do not use the
+ * interpolating synthesis (gcwt_plan_info.n_interp = 0).                                                */
+#define GCWT_WAVELET_MORLET 0x200
 
 /* The reference computes in float64 (transforms.py:142-143, convolution.py:68-77).  HIGH (the
  * default): x - mean and the forward FFT of every epoch in float64, and every decimation level cuts
