@@ -68,6 +68,7 @@ __global__ void __launch_bounds__(256) k_precision_predict(const float* __restri
   __shared__ float hout[kSpecBands];   // what the current level leaves out of band b: (1 - weight) h
   __shared__ float dens[256];
   __shared__ float gmin[kSpecBands];
+  __shared__ float gneg[kSpecBands];   // gmin of a shifted level's bins below zero frequency
   __shared__ int band_of[256];
   __shared__ float red[4];
   const int tid = threadIdx.x, slot = blockIdx.x;
@@ -105,6 +106,11 @@ __global__ void __launch_bounds__(256) k_precision_predict(const float* __restri
       dens[tid] = h[b] / fmaxf(1.0f, hi - lo) * per_bin;
       band_of[tid] = b;
     }
+    // A shifted level holds a band twice, below and above zero frequency, and a scale answers to the two copies with
+    // different gains (a Morlet scale to the lower one with next to none): each copy takes the minimum over its own
+    // bins.  One minimum over both gave the scales below the shift frequency an energy of their own of nearly zero,
+    // and a predicted loss far above what they lose (pink LFP at w0 = 5: 9.0e-6 predicted, rerouted for nothing).
+    float* const gm = tid < lv.band_shift ? gneg : gmin;
     __syncthreads();
     for (int s = 0; s < n_scales; ++s) {
       if (scale_level[s] != l) continue;                         // workgroup-uniform
@@ -112,11 +118,11 @@ __global__ void __launch_bounds__(256) k_precision_predict(const float* __restri
       const float g2 = g * g;
       // the scale's own energy, conservatively: a band's content counts with the SMALLEST gain the scale has on the
       // band's bins (a line may sit anywhere in its band, and a steep skirt -- gamma = 6 -- drops tenfold across one)
-      gmin[band_of[tid]] = 3.0e38f;
+      gm[band_of[tid]] = 3.0e38f;
       __syncthreads();
-      atomicMin(reinterpret_cast<unsigned*>(gmin) + band_of[tid], __float_as_uint(g2));
+      atomicMin(reinterpret_cast<unsigned*>(gm) + band_of[tid], __float_as_uint(g2));
       __syncthreads();
-      const float e_s = block_sum(gmin[band_of[tid]] * dens[tid], red);
+      const float e_s = block_sum(gm[band_of[tid]] * dens[tid], red);
       const float w_s = block_sum(g2, red) * (1.0f / 256.0f);
       // what the level leaves out, as the reference's L-tap kernel answers to it: flat side lobes above the band;
       // below it the response of a zero-mean kernel rises linearly from zero frequency to its first side lobe at

@@ -52,3 +52,68 @@ def band(w0, tol):
     xi_hi = xi[above[-1]] + step
     xi_neg = max(0.0, -(xi[above[0]] - step))
     return xi_hi, xi_neg
+
+
+def cwt_decimated(x, fs, freqs_hz, w0, epoch_bounds=None, plan=None, rows=None, B=256):
+    """Float64 model of what the engine computes for a Morlet plan, complex128 (len(rows), N): the structure of
+    decimated_model.cwt_decimated with H_s the closed form above.  The decisions -- method,
+    decimation, halo, hop per scale; band shift and low cut per level, a level found by (decimation, halo, hop) since
+    a Morlet plan can hold two levels of one decimation; FFT length per epoch -- are the planner's own (``plan``:
+    a CwtPlan of the layout, made here when omitted).  Whole epochs only (no time blocks)."""
+    import math
+    from scipy.fft import fft, ifft
+    from decimated_model import low_cut
+    from ghost_amd.engine import CwtPlan
+    from ghost_amd.wave import Morlet
+    from oracle import ghost_oracle as orc
+    x = np.asarray(x).squeeze().astype(np.float64)
+    x = x - x.mean()
+    n = x.size
+    epoch_bounds = np.array([[0, n]]) if epoch_bounds is None else np.asarray(epoch_bounds).reshape(-1, 2)
+    freqs_hz = np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64))
+    if plan is None:
+        plan = CwtPlan(n, 1, fs, freqs_hz, morlet_w0=w0, epoch_bounds=epoch_bounds, output="complex")
+    rows = list(range(len(freqs_hz))) if rows is None else list(rows)
+    si = plan.scale_info()
+    level_of = {(lv["decimation"], lv["halo"], lv["hop"]): lv for lv in plan.debug_levels()}
+    fft_len = {(a, b): p for (a, b, p) in plan.segments()}
+    out = np.zeros((len(rows), n), dtype=np.complex128)
+    k = np.arange(B)
+    for start, stop in epoch_bounds:
+        ne = stop - start
+        p_big = fft_len[(start, stop)]
+        lead = start - (start & ~63)                   # segments start on multiples of 64 samples
+        X = fft(np.concatenate([np.zeros(lead), x[start:stop]]), n=p_big)
+        xr_cache = {}
+        for o, i in enumerate(rows):
+            f, method = freqs_hz[i], si["method"][i]
+            if method in (1, 3):                       # time domain / block convolution: the literal kernel
+                psi = Morlet(w0=w0, freq=f, fs=fs).get_wavelet()
+                assert len(psi) == si["length"][i]
+                out[o, start:stop] = orc.overlap_add_convolve(x[start:stop], psi)
+                continue
+            if method == 2:                            # full band
+                H = response(2 * np.pi * np.arange(p_big) / p_big, w0, f, fs)
+                out[o, start:stop] = ifft(X * H)[lead:lead + ne]
+                continue
+            key = (int(si["decimation"][i]), int(si["halo"][i]), int(si["hop"][i]))
+            R, lh, hop = key
+            lv = level_of[key]
+            shift, M = lv["band_shift"], p_big // R
+            if key not in xr_cache:
+                sl = X[(np.arange(M) - shift * M // B) % p_big]
+                if not shift:
+                    sl = sl * low_cut(lv["low_cut"], p_big, M)
+                xr_cache[key] = ifft(sl) / R           # x_R: bin u stands for frequency u - shift M / B
+            xr = xr_cache[key]
+            H = response(2 * np.pi * (k - shift) / (B * R), w0, f, fs)
+            tw = np.exp(2j * np.pi * np.outer(k - shift, np.arange(R)) / (B * R))
+            nblk = int(math.ceil(math.ceil((lead + ne) / R) / hop))
+            first = np.arange(nblk) * hop - lh
+            XB = fft(xr[(first[:, None] + k[None, :]) % M], axis=1)
+            blk = ifft((XB * H)[:, :, None] * tw[None], axis=1)                    # [b, m, r]
+            if shift:      # the carrier of the shifted band: block position and sample within the block
+                blk = blk * np.exp(-2j * np.pi * shift * (first[:, None] + k[None, :]) / B)[:, :, None]
+            y = blk[:, lh:lh + hop, :].reshape(-1)
+            out[o, start:stop] = y[lead:lead + ne]
+    return out

@@ -6,27 +6,12 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
-from oracle import ghost_oracle as orc
+from morlet_cases import truth as _truth
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
 CASES = [(6.0, 1000.0), (5.0, 1250.0), (10.0, 30000.0)]
-
-
-def _truth(x, fs, freqs, w0, rows=None, bounds=None):
-    """complex128 rows of one channel: per epoch, overlap_add_convolve(x - mean(x), psi_f, 'same'); 0 between."""
-    from ghost_amd.wave import Morlet
-    x64 = np.asarray(x, dtype=np.float64)
-    xc = x64 - x64.mean()                                    # the global mean (transforms.py:142-143)
-    rows = range(len(freqs)) if rows is None else rows
-    bounds = [(0, x64.size)] if bounds is None else bounds
-    out = np.zeros((len(rows), x64.size), dtype=np.complex128)
-    for i, r in enumerate(rows):
-        psi = Morlet(w0=w0, freq=freqs[r], fs=fs).get_wavelet()
-        for a, b in bounds:
-            out[i, a:b] = orc.overlap_add_convolve(xc[a:b], psi, mode="same")
-    return out
 
 
 def _as(output, c):
