@@ -11,7 +11,8 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 
-__all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "set_option", "device_count", "device_name", "device_memory"]
+__all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "set_option",
+           "device_count", "device_name", "device_memory"]
 
 
 def set_option(name, value=None):
@@ -146,6 +147,119 @@ def output_stride_value(stride):
     if int(stride) < 1:
         raise ValueError("output_stride must be an integer >= 1, not %d" % int(stride))
     return int(stride)
+
+
+def coherence_pairs(pairs, seed, n_channels):
+    """The channel pairs of a coherence() call as a (P, 2) int32 array.  ``pairs=None, seed=None``: all (a, b), a < b, in
+    lexicographic order; ``seed=c``: (c, k) for every k != c, k ascending; else ``pairs``: (P, 2) integers, a != b, both
+    in [0, n_channels).  Anything else -- floats, bools, a == b, an index out of range, ``pairs`` and ``seed`` together
+    -- raises ValueError."""
+    n = int(n_channels)
+    if n < 2:
+        raise ValueError("coherence needs at least 2 channels, not %d" % n)
+    if pairs is not None and seed is not None:
+        raise ValueError("'pairs' and 'seed' cannot both be used")
+    if pairs is None and seed is None:
+        a, b = np.triu_indices(n, 1)
+        return np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.int32)
+    if pairs is None:
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)):
+            raise ValueError("'seed' must be a channel index (an integer), not %r" % (seed,))
+        if not 0 <= int(seed) < n:
+            raise ValueError("'seed' %d is not a channel of the result (0 .. %d)" % (int(seed), n - 1))
+        others = np.array([k for k in range(n) if k != int(seed)], dtype=np.int32)
+        return np.ascontiguousarray(np.stack([np.full_like(others, int(seed)), others], axis=1))
+    arr = np.asarray(pairs)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("'pairs' must be an array of integer channel indices, not %s" % arr.dtype)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1:
+        raise ValueError("'pairs' must have shape (P, 2), P >= 1, not %r" % (arr.shape,))
+    if arr.min() < 0 or arr.max() >= n:
+        raise ValueError("'pairs' names a channel outside 0 .. %d" % (n - 1))
+    if np.any(arr[:, 0] == arr[:, 1]):
+        raise ValueError("'pairs' holds a channel paired with itself")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def coherence_window(window):
+    """The bin width as an int: an integer >= 2 (numpy integers too); anything else raises ValueError."""
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
+        raise ValueError("window must be an integer >= 2 (columns per bin), not %r" % (window,))
+    if int(window) < 2:
+        raise ValueError("window must be an integer >= 2 (columns per bin), not %d" % int(window))
+    return int(window)
+
+
+class CoherenceResult:
+    """What coherence() left on the device: ``coherence`` (P, S, B) float32, ``cross`` (P, S, B) complex64 and ``power``
+    (C, S, B) float32 in one DeviceBuffer, rows ``pitch`` elements apart; ``pairs`` (P, 2); ``window``; ``counts`` (B,):
+    the columns of each bin.  ``to_host()`` brings the three over."""
+
+    def __init__(self, buffer, pairs, n_channels, n_scales, n_bins, pitch, window, counts):
+        self.buffer, self.pairs, self.pitch, self.window, self.counts = buffer, pairs, int(pitch), int(window), counts
+        self.n_pairs, self.n_channels, self.n_scales, self.n_bins = len(pairs), int(n_channels), int(n_scales), int(n_bins)
+
+    # the buffer holds cross, then coherence, then power
+    def _offsets(self):
+        rows = self.n_pairs * self.n_scales * self.pitch
+        return 0, rows * 8, rows * 12
+
+    @property
+    def nbytes(self):
+        return (3 * self.n_pairs + self.n_channels) * self.n_scales * self.pitch * 4
+
+    def to_host(self):
+        """{"coherence", "cross", "power"}: dense ndarrays."""
+        p, c, s, b = self.n_pairs, self.n_channels, self.n_scales, self.n_bins
+        o_cross, o_coh, o_pow = self._offsets()
+        cross = self.buffer.download((p, s, self.pitch), np.complex64, o_cross)[..., :b]
+        coh = self.buffer.download((p, s, self.pitch), np.float32, o_coh)[..., :b]
+        power = self.buffer.download((c, s, self.pitch), np.float32, o_pow)[..., :b]
+        return {"coherence": np.ascontiguousarray(coh), "cross": np.ascontiguousarray(cross),
+                "power": np.ascontiguousarray(power)}
+
+    def free(self):
+        if self.buffer is not None:
+            self.buffer.free()
+            self.buffer = None
+
+
+def coherence(result, pairs, window):
+    """Binned cross-spectra of channel pairs of a complex DeviceResult, computed where it lies (gcwt_coherence: bins of
+    ``window`` columns; include/ghostcwt.h has the definition).  ``pairs``: (P, 2) as coherence_pairs returns them.  The
+    result itself is only read.  -> CoherenceResult."""
+    window = coherence_window(window)
+    if not isinstance(result, DeviceResult):
+        raise ValueError("coherence() takes a DeviceResult on one device (the channels of a result sharded over "
+                         "several GPUs cannot be paired)")
+    if result.buffer is None:
+        raise ValueError("the result has been freed")
+    if not result.is_complex:
+        raise ValueError("coherence() needs complex coefficients (output='complex')")
+    c, s, n = result.shape
+    pairs = coherence_pairs(pairs, None, c)
+    n_bins = -(-n // window)
+    pitch = (n_bins + 31) & ~31
+    p = len(pairs)
+    nbytes = (3 * p + c) * s * pitch * 4
+    free, _ = device_memory()
+    if nbytes > free:
+        raise MemoryError("coherence() needs %d bytes on the device for its outputs (%d pairs, %d channels, %d "
+                          "scales, %d bins) and %d are free: fewer pairs or a wider window"
+                          % (nbytes, p, c, s, n_bins, free))
+    buf = DeviceBuffer(nbytes)
+    res = CoherenceResult(buf, pairs, c, s, n_bins, pitch, window,
+                          np.minimum(window, n - np.arange(n_bins, dtype=np.int64) * window))
+    o_cross, o_coh, o_pow = res._offsets()
+    base = buf.ptr.value
+    try:
+        check(lib.gcwt_coherence(result.buffer.ptr, result.pitch, c, s, n, pairs.ctypes.data_as(C.POINTER(C.c_int32)), p,
+                                 window, C.c_void_p(base + o_pow), C.c_void_p(base + o_cross), C.c_void_p(base + o_coh),
+                                 pitch))
+    except Exception:
+        res.free()
+        raise
+    return res
 
 
 def stride_columns(start, stop, stride):

@@ -31,6 +31,14 @@ class WaveletTransform:
         return self.__class__.__name__
 
 
+class _Coherence:
+    """What ContinuousWaveletTransform.coherence returns (host arrays)."""
+
+    def __init__(self, coherence, cross, power, pairs, frequencies, time, window):
+        self.coherence, self.cross, self.power, self.pairs = coherence, cross, power, pairs
+        self.frequencies, self.time, self.window = frequencies, time, window
+
+
 class ContinuousWaveletTransform(WaveletTransform):
     """Continuous wavelet transform.
 
@@ -311,6 +319,44 @@ class ContinuousWaveletTransform(WaveletTransform):
         else:
             res = self._device_result.to_host(np.float64 if wide else np.float32, scales, start, stop)
         return res[0] if squeeze else res
+
+    def coherence(self, pairs=None, *, seed=None, window):
+        """Wavelet coherence and cross-spectra between channels of the last transform, reduced on the device over bins
+        of ``window`` columns (an integer >= 2; with an output stride K a column is K samples) -- the transform must
+        have been ``multichannel=True, output='complex'`` with at least 2 channels on one device.  ``pairs``: (P, 2)
+        channel indices; ``seed=c``: channel c against every other; neither: all pairs a < b.  With Sxy the sum of
+        W[a] conj(W[b]) over a bin of cnt columns, Sxx and Syy those of |W[a]|^2 and |W[b]|^2, the returned object has
+        ``coherence`` (P, S, B) float32 = |Sxy|^2 / (Sxx Syy) in [0, 1], ``cross`` (P, S, B) complex64 = Sxy / cnt
+        (angle > 0: channel b lags channel a), ``power`` (C, S, B) float32 = Sxx / cnt of every channel, ``pairs``
+        (P, 2), ``frequencies`` (S,), ``time`` (B,): the time of each bin's first column, and ``window``.  Bins are
+        plain column ranges, B = ceil(columns / window), the last one may be short; a bin inside a gap between epochs
+        is exactly 0 in all three.  A bin shorter than the wavelet's duration at a scale reads close to 1 whatever
+        the signals -- a property of the estimator (one effective sample), not an error: choose ``window`` as several
+        periods of the lowest frequency of interest.  Only the reduced arrays cross to the host; the resident result,
+        ``fetch()`` and the result attributes are untouched."""
+        from .. import engine
+        window = engine.coherence_window(window)
+        if self._device_result is None or (self._pending is None and self._last_kind is None):
+            raise ValueError("no transform on the device (call transform() first)")
+        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
+        if out_kind != "complex":
+            raise ValueError("coherence() needs the complex coefficients: the last transform was output='%s', "
+                             "not output='complex'" % out_kind)
+        if not isinstance(self._device_result, engine.DeviceResult):
+            raise ValueError("coherence() pairs channels on one device: the last transform was sharded over several "
+                             "(devices=[...]), and pairs across devices are not supported")
+        if squeeze or self._device_result.shape[0] < 2:
+            raise ValueError("coherence() relates channels: the last transform must be multichannel=True with at "
+                             "least 2 channels")
+        pairs = engine.coherence_pairs(pairs, seed, self._device_result.shape[0])
+        res = engine.coherence(self._device_result, pairs, window)
+        try:
+            out = res.to_host()
+        finally:
+            res.free()
+        t = self.time
+        return _Coherence(out["coherence"], out["cross"], out["power"], pairs.astype(np.int64),
+                          np.array(self._frequencies), None if t is None else np.asarray(t)[::window], window)
 
     def release_device(self):
         """Frees the device copy of the last result (bringing it over first if nothing has asked for it yet)."""

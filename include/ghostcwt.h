@@ -207,6 +207,23 @@ int gcwt_host_free(void* ptr);
  * access, and how any (scale, sample) range of a result is read without moving the rest (transforms.py:496-527). */
 int gcwt_rows_to_host(const float* d_src, int64_t src_pitch, int64_t n_rows, int64_t row_elems, void* dst,
                       int64_t dst_pitch, int flags);
+/* Binned cross-spectra of channel pairs from a device-resident complex result, on the device that holds it
+ * (csrc/coherence.hip).  pairs: n_pairs x 2 channel indices (a != b, both < n_channels).  d_rows: complex64 rows
+ * [channel][scale] pitch elements apart, as gcwt_execute leaves them with GCWT_OUT_ON_DEVICE and out_mode complex.
+ * Bin m holds the columns [m window, min((m + 1) window, n_cols)), window >= 2; there are B = ceil(n_cols / window)
+ * bins of cnt_m columns.  With Sxy = sum W[a] conj(W[b]), Sxx = sum |W[a]|^2 and Syy = sum |W[b]|^2 over a bin:
+ *   d_cross [P][S][B]     complex64  Sxy / cnt_m   (angle > 0: channel b lags channel a)
+ *   d_power [C][S][B]     float32    Sxx / cnt_m, every channel
+ *   d_coherence [P][S][B] float32    |Sxy|^2 / (Sxx Syy) in [0, 1]; exactly 0 where Sxx Syy == 0 (bins inside an
+ *                                    epoch gap: all three outputs are 0 there)
+ * Any of the three may be NULL; their rows are out_pitch (>= B) elements apart.  The sums are float32 in a fixed order
+ * that does not depend on which other pairs are asked for: a pair gives the same bits alone and among all pairs.
+ * A bin shorter than the wavelet's duration at a scale reads close to 1 whatever the signals: a property of the
+ * estimator.  Plan-independent, like gcwt_rows_to_host; the device is the one that holds d_rows.  Arguments are
+ * checked before any device call (GCWT_ERR_INVALID). */
+int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                   const int32_t* pairs, int32_t n_pairs, int64_t window,
+                   float* d_power, float* d_cross, float* d_coherence, int64_t out_pitch);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

@@ -106,6 +106,20 @@ int gcwt_debug_check_output(const void* out_device, int64_t row_pitch_floats, in
                             int32_t rows_per_channel, int32_t n_channels, int32_t distinct,
                             int64_t* n_nonfinite, int64_t* n_mismatched);
 
+
+/* Host only: the tasks gcwt_coherence cuts a pair list into.  Channels form tiles of GCWT_COHERENCE_TILE; a task is
+ * one (tile_a <= tile_b) -- times every scale and run of bins -- and accumulates the cells (i, j) = channel i of tile
+ * a with channel j of tile b that its entries name.  entries: n_pairs x 3 = (cell i * GCWT_COHERENCE_TILE + j,
+ * conjugate, output row = index into pairs); entry_first [n_tasks + 1]: task t owns entries [entry_first[t],
+ * entry_first[t + 1]).  conjugate = 1: the pair was asked for as (channel of the cell's j, channel of its i).  flags:
+ * bit 0 / 1 -- the task writes the power rows of tile a's / tile b's channels; every tile is written by exactly one
+ * task, and tiles that no pair touches get a task of their own without entries, after all others.  Returns the
+ * number of tasks (arrays, any of which may be NULL, are filled when max_tasks holds them) or an error code < 0. */
+enum { GCWT_COHERENCE_TILE = 8 };
+int gcwt_debug_coherence_tasks(int32_t n_channels, const int32_t* pairs, int32_t n_pairs, int32_t* tile_a,
+                               int32_t* tile_b, int32_t* flags, int32_t* entry_first, int32_t* entries,
+                               int32_t max_tasks);
+
 #ifdef __cplusplus
 }
 #endif
