@@ -81,6 +81,8 @@ def _load():
         "gcwt_rows_to_host": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int]),
         "gcwt_coherence": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_int64, vp, vp, vp,
                                      C.c_int64]),
+        "gcwt_coupling": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int64, vp, vp, vp, C.c_int64]),
         "gcwt_plan_create": (C.c_int, [C.POINTER(vp), C.POINTER(Params)]),
         "gcwt_plan_destroy": (None, [vp]),
         "gcwt_plan_get_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
@@ -127,6 +129,7 @@ def _load():
         "gcwt_debug_check_output": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i64p, i64p]),
         "gcwt_debug_bandwidth": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_double)]),
         "gcwt_debug_coherence_tasks": (C.c_int, [C.c_int32, i32p, C.c_int32, i32p, i32p, i32p, i32p, i32p, C.c_int32]),
+        "gcwt_debug_coupling_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, i32p, i64p, i64p, i64p]),
         "gcwt_debug_fetch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int64]),
     }
     for name, (res, args) in sig.items():

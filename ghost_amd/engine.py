@@ -11,7 +11,8 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 
-__all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "set_option",
+__all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
+           "coupling", "coupling_rows", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -256,6 +257,115 @@ def coherence(result, pairs, window):
         check(lib.gcwt_coherence(result.buffer.ptr, result.pitch, c, s, n, pairs.ctypes.data_as(C.POINTER(C.c_int32)), p,
                                  window, C.c_void_p(base + o_pow), C.c_void_p(base + o_cross), C.c_void_p(base + o_coh),
                                  pitch))
+    except Exception:
+        res.free()
+        raise
+    return res
+
+
+def coupling_rows(limits, frequencies, what):
+    """The rows of a coupling() band as (first, count): those whose frequency lies in the closed interval ``limits`` =
+    (f_lo, f_hi) in Hz, f_lo <= f_hi.  ``frequencies`` is monotonic (descending for the default grid, ascending for
+    ``freqs=``), so the rows are one contiguous run.  ``what`` ('phase', 'amplitude') names the band in the ValueError
+    that anything else raises: not two finite numbers, f_lo > f_hi, no row inside."""
+    try:
+        ok = not isinstance(limits, (str, bytes)) and len(limits) == 2 and not any(
+            isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in limits)
+    except TypeError:
+        ok = False
+    if not ok or not all(np.isfinite(float(v)) for v in limits):
+        raise ValueError("'%s' must be (f_lo, f_hi) in Hz, two finite numbers, not %r" % (what, limits))
+    lo, hi = float(limits[0]), float(limits[1])
+    if lo > hi:
+        raise ValueError("'%s' must be (f_lo, f_hi) with f_lo <= f_hi, not %r" % (what, limits))
+    f = np.asarray(frequencies, dtype=np.float64).ravel()
+    rows = np.flatnonzero((f >= lo) & (f <= hi))
+    if rows.size == 0:
+        raise ValueError("'%s': no row of the transform has its frequency in [%g, %g] Hz (the rows span %g .. %g Hz)"
+                         % (what, lo, hi, f.min() if f.size else np.nan, f.max() if f.size else np.nan))
+    if rows[-1] - rows[0] + 1 != rows.size:
+        raise ValueError("'%s': the frequencies are not monotonic" % what)
+    return int(rows[0]), int(rows.size)
+
+
+class CouplingResult:
+    """What coupling() left on the device: ``vector`` (C, P, A, B) complex64, ``mvl`` (C, P, A, B) float32 and
+    ``amplitude`` (C, A, B) float32 in one DeviceBuffer, rows ``pitch`` elements apart; ``phase_rows`` and ``amp_rows``:
+    (first, count); ``window``; ``counts`` (B,): the columns of each bin.  ``to_host()`` brings the three over."""
+
+    def __init__(self, buffer, n_channels, phase_rows, amp_rows, n_bins, pitch, window, counts):
+        self.buffer, self.pitch, self.window, self.counts = buffer, int(pitch), int(window), counts
+        self.phase_rows, self.amp_rows = tuple(phase_rows), tuple(amp_rows)
+        self.n_channels, self.n_phase, self.n_amp, self.n_bins = int(n_channels), int(phase_rows[1]), int(amp_rows[1]), int(n_bins)
+
+    # the buffer holds vector, then mvl, then amplitude
+    def _offsets(self):
+        rows = self.n_channels * self.n_phase * self.n_amp * self.pitch
+        return 0, rows * 8, rows * 12
+
+    @property
+    def nbytes(self):
+        return (3 * self.n_phase + 1) * self.n_channels * self.n_amp * self.pitch * 4
+
+    def to_host(self):
+        """{"vector", "mvl", "amplitude"}: dense ndarrays."""
+        c, p, a, b = self.n_channels, self.n_phase, self.n_amp, self.n_bins
+        o_vec, o_mvl, o_amp = self._offsets()
+        vec = self.buffer.download((c, p, a, self.pitch), np.complex64, o_vec)[..., :b]
+        mvl = self.buffer.download((c, p, a, self.pitch), np.float32, o_mvl)[..., :b]
+        amp = self.buffer.download((c, a, self.pitch), np.float32, o_amp)[..., :b]
+        return {"vector": np.ascontiguousarray(vec), "mvl": np.ascontiguousarray(mvl),
+                "amplitude": np.ascontiguousarray(amp)}
+
+    def free(self):
+        if self.buffer is not None:
+            self.buffer.free()
+            self.buffer = None
+
+
+def _row_range(rows, n_scales, what):
+    try:
+        first, count = rows
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in (first, count))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or first < 0 or count < 1 or first + count > n_scales:
+        raise ValueError("%s must be (first, count), a non-empty run of the result's %d rows, not %r" % (what, n_scales, rows))
+    return int(first), int(count)
+
+
+def coupling(result, phase_rows, amp_rows, window):
+    """Binned phase-amplitude coupling inside every channel of a complex DeviceResult, computed where it lies
+    (gcwt_coupling: bins of ``window`` columns; include/ghostcwt.h has the definition).  ``phase_rows``, ``amp_rows``:
+    (first, count) as coupling_rows returns them; they may overlap.  The result itself is only read.  -> CouplingResult."""
+    window = coherence_window(window)
+    if not isinstance(result, DeviceResult):
+        raise ValueError("coupling() takes a DeviceResult on one device (a result sharded over several GPUs is not "
+                         "supported)")
+    if result.buffer is None:
+        raise ValueError("the result has been freed")
+    if not result.is_complex:
+        raise ValueError("coupling() needs complex coefficients (output='complex')")
+    c, s, n = result.shape
+    phase_rows = _row_range(phase_rows, s, "phase_rows")
+    amp_rows = _row_range(amp_rows, s, "amp_rows")
+    n_bins = -(-n // window)
+    pitch = (n_bins + 31) & ~31
+    res = CouplingResult(None, c, phase_rows, amp_rows, n_bins, pitch, window,
+                         np.minimum(window, n - np.arange(n_bins, dtype=np.int64) * window))
+    nbytes = res.nbytes
+    free, _ = device_memory()
+    if nbytes > free:
+        raise MemoryError("coupling() needs %d bytes on the device for its outputs (%d channels, %d x %d rows, %d bins) "
+                          "and %d are free: narrower bands or a wider window"
+                          % (nbytes, c, phase_rows[1], amp_rows[1], n_bins, free))
+    res.buffer = buf = DeviceBuffer(nbytes)
+    o_vec, o_mvl, o_amp = res._offsets()
+    base = buf.ptr.value
+    try:
+        check(lib.gcwt_coupling(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1], amp_rows[0],
+                                amp_rows[1], window, C.c_void_p(base + o_vec), C.c_void_p(base + o_mvl),
+                                C.c_void_p(base + o_amp), pitch))
     except Exception:
         res.free()
         raise

@@ -39,6 +39,15 @@ class _Coherence:
         self.frequencies, self.time, self.window = frequencies, time, window
 
 
+class _Coupling:
+    """What ContinuousWaveletTransform.coupling returns (host arrays)."""
+
+    def __init__(self, mvl, vector, amplitude, phase_frequencies, amplitude_frequencies, time, window):
+        self.mvl, self.vector, self.amplitude = mvl, vector, amplitude
+        self.phase_frequencies, self.amplitude_frequencies = phase_frequencies, amplitude_frequencies
+        self.time, self.window = time, window
+
+
 class ContinuousWaveletTransform(WaveletTransform):
     """Continuous wavelet transform.
 
@@ -357,6 +366,48 @@ class ContinuousWaveletTransform(WaveletTransform):
         t = self.time
         return _Coherence(out["coherence"], out["cross"], out["power"], pairs.astype(np.int64),
                           np.array(self._frequencies), None if t is None else np.asarray(t)[::window], window)
+
+    def coupling(self, *, phase, amplitude, window):
+        """Phase-amplitude coupling inside each channel of the last transform -- does the amplitude of a fast band ride
+        on the phase of a slow one? --, reduced on the device over bins of ``window`` columns (an integer >= 2; with
+        an output stride K a column is K samples).  The transform must have been ``output='complex'`` on one device.
+        ``phase`` and ``amplitude``: (f_lo, f_hi) in Hz; the rows whose frequency lies in the closed interval (P phase
+        rows, A amplitude rows; the bands may overlap).  With u = W[p] / |W[p]| (0 where that is 0), M the sum of
+        |W[a]| u over a bin of cnt columns and S that of |W[a]|, the returned object has ``vector`` (C, P, A, B)
+        complex64 = M / cnt (its angle: the phase of row p at which row a is strongest), ``mvl`` (C, P, A, B) float32 =
+        |M| / S in [0, 1], the normalised mean vector length (0: no preferred phase, 1: all amplitude at one phase),
+        ``amplitude`` (C, A, B) float32 = S / cnt, ``phase_frequencies`` (P,), ``amplitude_frequencies`` (A,),
+        ``time`` (B,): the time of each bin's first column, and ``window``; after the reference's single-channel call
+        the channel axis is dropped.  Bins are plain column ranges, B = ceil(columns / window), the last one may be
+        short; a bin inside a gap between epochs is exactly 0 in all three.  A bin shorter than about one period of
+        the phase row reads high whatever the signal -- a property of the estimator (one effective sample), not an
+        error: choose ``window`` as several periods of the lowest phase frequency.  No surrogate statistics are made.
+        Only the reduced arrays cross to the host; the resident result, ``fetch()`` and the result attributes are
+        untouched."""
+        from .. import engine
+        window = engine.coherence_window(window)
+        if self._device_result is None or (self._pending is None and self._last_kind is None):
+            raise ValueError("no transform on the device (call transform() first)")
+        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
+        if out_kind != "complex":
+            raise ValueError("coupling() needs the complex coefficients: the last transform was output='%s', "
+                             "not output='complex'" % out_kind)
+        if not isinstance(self._device_result, engine.DeviceResult):
+            raise ValueError("coupling() works on one device: the last transform was sharded over several "
+                             "(devices=[...]), which is not supported")
+        f = np.array(self._frequencies)
+        phase_rows = engine.coupling_rows(phase, f, "phase")
+        amp_rows = engine.coupling_rows(amplitude, f, "amplitude")
+        res = engine.coupling(self._device_result, phase_rows, amp_rows, window)
+        try:
+            out = res.to_host()
+        finally:
+            res.free()
+        if squeeze:
+            out = {k: v[0] for k, v in out.items()}
+        t = self.time
+        return _Coupling(out["mvl"], out["vector"], out["amplitude"], f[phase_rows[0]:phase_rows[0] + phase_rows[1]],
+                         f[amp_rows[0]:amp_rows[0] + amp_rows[1]], None if t is None else np.asarray(t)[::window], window)
 
     def release_device(self):
         """Frees the device copy of the last result (bringing it over first if nothing has asked for it yet)."""

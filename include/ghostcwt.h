@@ -224,6 +224,24 @@ int gcwt_rows_to_host(const float* d_src, int64_t src_pitch, int64_t n_rows, int
 int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                    const int32_t* pairs, int32_t n_pairs, int64_t window,
                    float* d_power, float* d_cross, float* d_coherence, int64_t out_pitch);
+/* Binned phase-amplitude coupling inside every channel of a device-resident complex result, on the device that holds
+ * it (csrc/coupling.hip): does the amplitude of row a ride on the phase of row p?  d_rows, pitch, n_cols, window and
+ * the bins are those of gcwt_coherence.  Phase rows [phase_first, phase_first + n_phase) = P rows and amplitude rows
+ * [amp_first, amp_first + n_amp) = A rows, both inside [0, n_scales); they may overlap.  With u_p = W[c][p] / |W[c][p]|
+ * (0 where that is 0), M = sum |W[c][a]| u_p and S = sum |W[c][a]| over a bin:
+ *   d_vector [C][P][A][B]  complex64  M / cnt_m    (its angle: the phase of row p at which row a is strongest)
+ *   d_mvl [C][P][A][B]     float32    |M| / S in [0, 1], the normalised mean vector length; exactly 0 where S == 0
+ *   d_amplitude [C][A][B]  float32    S / cnt_m
+ * Any of the three may be NULL; their rows are out_pitch (>= B) elements apart.  Bins inside an epoch gap are exactly
+ * 0 in all three.  The sums are float32 in gcwt_coherence's fixed order and the normalisation is a prescribed sequence
+ * of correctly rounded operations (coupling.hip), neither depending on which other rows are asked for: a cell (p, a)
+ * gives the same bits alone and inside any larger ranges.  A bin shorter than about one period of the phase row reads
+ * high whatever the signal (one effective sample): a property of the estimator; no surrogate statistics are made.
+ * Plan-independent; the device is the one that holds d_rows.  Arguments are checked before any device call
+ * (GCWT_ERR_INVALID). */
+int gcwt_coupling(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                  int32_t phase_first, int32_t n_phase, int32_t amp_first, int32_t n_amp, int64_t window,
+                  float* d_vector, float* d_mvl, float* d_amplitude, int64_t out_pitch);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

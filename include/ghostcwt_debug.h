@@ -120,6 +120,16 @@ int gcwt_debug_coherence_tasks(int32_t n_channels, const int32_t* pairs, int32_t
                                int32_t* tile_b, int32_t* flags, int32_t* entry_first, int32_t* entries,
                                int32_t max_tasks);
 
+/* Host only: the grid gcwt_coupling launches.  The phase rows form tiles of GCWT_COUPLING_TILE_PHASE and the amplitude
+ * rows tiles of GCWT_COUPLING_TILE_AMP, counted from the first row of each range (the last tile of either may be
+ * ragged); a workgroup takes one (channel, run of run_bins bins, phase tile, amplitude tile).  n_blocks counts the
+ * workgroups: every tile of every (channel, run), the (channel, run)s padded to a multiple of 8 so that the tiles of
+ * one of them lie 8 workgroups apart.  Any pointer may be NULL.  Returns GCWT_OK or an error code < 0. */
+enum { GCWT_COUPLING_TILE_PHASE = 4, GCWT_COUPLING_TILE_AMP = 8 };
+int gcwt_debug_coupling_grid(int32_t n_channels, int64_t n_cols, int32_t n_phase, int32_t n_amp, int64_t window,
+                             int32_t* n_phase_tiles, int32_t* n_amp_tiles, int64_t* run_bins, int64_t* n_runs,
+                             int64_t* n_blocks);
+
 #ifdef __cplusplus
 }
 #endif
