@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
-           "coupling", "coupling_rows", "set_option",
+           "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -366,6 +366,155 @@ def coupling(result, phase_rows, amp_rows, window):
         check(lib.gcwt_coupling(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1], amp_rows[0],
                                 amp_rows[1], window, C.c_void_p(base + o_vec), C.c_void_p(base + o_mvl),
                                 C.c_void_p(base + o_amp), pitch))
+    except Exception:
+        res.free()
+        raise
+    return res
+
+
+def _seconds(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(float(value)) or float(value) < 0:
+        raise ValueError("'%s' must be a finite number of seconds >= 0, not %r" % (what, value))
+    return float(value)
+
+
+def _trigger_scan(events, time, fs, stride, before, after, n_cols):
+    """trigger_columns plus why events were dropped: {"gap": not within half a column period of any column, "edge": the
+    window leaves the columns, "splice": the window would join two epochs} -> counts."""
+    before, after = _seconds(before, "before"), _seconds(after, "after")
+    try:
+        ev = np.asarray(events)
+        ok = ev.ndim == 1 and ev.dtype != np.bool_ and (np.issubdtype(ev.dtype, np.integer) or np.issubdtype(ev.dtype, np.floating))
+    except Exception:
+        ok = False
+    if not ok:
+        raise ValueError("'events' must be a 1-D array of event times in seconds (finite numbers), not %r"
+                         % (getattr(events, "shape", None) if hasattr(events, "dtype") else events,))
+    ev = ev.astype(np.float64)
+    if not np.all(np.isfinite(ev)):
+        raise ValueError("'events' must be finite: entry %d is %r" % (int(np.flatnonzero(~np.isfinite(ev))[0]),
+                                                                      float(ev[~np.isfinite(ev)][0])))
+    period = float(stride) / float(fs)                      # seconds per column
+    nb, na = int(round(before / period)), int(round(after / period))
+    if time is None:
+        col = np.clip(np.rint(ev / period), -1, 2.0 ** 62).astype(np.int64)      # (-1: before the first sample)
+        near = col >= 0 if n_cols is None else (col >= 0) & (col < n_cols)
+        t = None
+    else:
+        t = np.asarray(time, dtype=np.float64).ravel()
+        n_cols = t.size if n_cols is None else min(int(n_cols), t.size)
+        t = t[:n_cols]
+        if n_cols == 0:
+            raise ValueError("'time' holds no column")
+        hi = np.clip(np.searchsorted(t, ev), 0, n_cols - 1)
+        lo = np.clip(hi - 1, 0, None)
+        col = np.where(np.abs(t[lo] - ev) <= np.abs(t[hi] - ev), lo, hi).astype(np.int64)
+        near = np.abs(t[col] - ev) <= 0.5 * period
+    inside = near & (col - nb >= 0) & (True if n_cols is None else col + na < n_cols)
+    whole = inside.copy()
+    if t is not None and inside.any():
+        span = t[np.where(inside, col + na, 0)] - t[np.where(inside, col - nb, 0)]
+        whole &= np.abs(span - (nb + na) * period) <= 0.5 / float(fs)
+    reasons = {"gap": int(np.count_nonzero(~near)), "edge": int(np.count_nonzero(near & ~inside)),
+               "splice": int(np.count_nonzero(inside & ~whole))}
+    return np.ascontiguousarray(col[whole], dtype=np.int64), whole, nb, na, reasons
+
+
+def trigger_columns(events, time, fs, stride, before, after, n_cols=None):
+    """Event times -> the columns triggered() gathers around.  ``events``: 1-D, seconds on the clock of ``time`` (the
+    times of the result's columns, ``ContinuousWaveletTransform.time``; None: seconds from the first sample, column j at
+    j stride / fs -- ``n_cols`` then bounds the columns).  ``before``, ``after``: seconds >= 0, nb = round(before fs /
+    stride) columns and na likewise.  An event maps to its nearest column and is dropped when that column is more than
+    half a column period away (the event lies in a gap between epochs or outside the recording), when its window leaves
+    [0, n_cols), or when time[col + na] - time[col - nb] differs from (nb + na) stride / fs by more than half a sample
+    period (the window would splice two epochs).  -> (cols int64: the surviving events' columns in the order given,
+    used: bool mask over ``events``, nb, na).  ValueError naming 'events', 'before' or 'after' for anything that is not a
+    1-D array of finite numbers or a finite number >= 0."""
+    return _trigger_scan(events, time, fs, stride, before, after, n_cols)[:4]
+
+
+class TriggeredResult:
+    """What triggered() left on the device, each (C, R, L) with rows ``pitch`` elements apart in one DeviceBuffer:
+    ``evoked`` and ``vector`` complex64, ``amplitude``, ``power`` and ``itpc`` float32; ``rows``: (first, count);
+    ``n_before``, ``n_after`` columns, L = n_before + n_after + 1 lags; ``n_events``.  ``to_host()`` brings the five over."""
+
+    def __init__(self, buffer, n_channels, rows, n_before, n_after, pitch, n_events):
+        self.buffer, self.pitch, self.rows = buffer, int(pitch), tuple(rows)
+        self.n_channels, self.n_rows, self.n_events = int(n_channels), int(rows[1]), int(n_events)
+        self.n_before, self.n_after, self.n_lags = int(n_before), int(n_after), int(n_before) + int(n_after) + 1
+
+    # the buffer holds evoked, vector, then amplitude, power, itpc
+    def _offsets(self):
+        plane = self.n_channels * self.n_rows * self.pitch * 4
+        return {"evoked": 0, "vector": 2 * plane, "amplitude": 4 * plane, "power": 5 * plane, "itpc": 6 * plane}
+
+    @property
+    def nbytes(self):
+        return 7 * self.n_channels * self.n_rows * self.pitch * 4
+
+    def to_host(self):
+        """{"amplitude", "power", "evoked", "vector", "itpc"}: dense ndarrays."""
+        shape = (self.n_channels, self.n_rows, self.pitch)
+        return {name: np.ascontiguousarray(self.buffer.download(shape, np.complex64 if name in ("evoked", "vector")
+                                                                else np.float32, off)[..., :self.n_lags])
+                for name, off in self._offsets().items()}
+
+    def free(self):
+        if self.buffer is not None:
+            self.buffer.free()
+            self.buffer = None
+
+
+def _columns(value, what):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < 0:
+        raise ValueError("%s must be an integer number of columns >= 0, not %r" % (what, value))
+    return int(value)
+
+
+def triggered(result, cols, nb, na, rows=None):
+    """Event-locked averages of the rows of a complex DeviceResult, computed where it lies (gcwt_triggered;
+    include/ghostcwt.h has the definition): around every event column of ``cols`` (1-D integers, in this order; the order
+    is part of the definition of the float32 sums) the window of ``nb`` columns before and ``na`` after, which must lie
+    inside the result for every event -- trigger_columns() makes such a list from event times.  ``rows``: (first, count),
+    default all rows.  The result itself is only read.  -> TriggeredResult."""
+    if not isinstance(result, DeviceResult):
+        raise ValueError("triggered() takes a DeviceResult on one device (a result sharded over several GPUs is not "
+                         "supported)")
+    if result.buffer is None:
+        raise ValueError("the result has been freed")
+    if not result.is_complex:
+        raise ValueError("triggered() needs complex coefficients (output='complex')")
+    c, s, n = result.shape
+    nb, na = _columns(nb, "nb"), _columns(na, "na")
+    rows = _row_range((0, s) if rows is None else rows, s, "rows")
+    arr = np.asarray(cols)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer) or arr.ndim != 1:
+        raise ValueError("cols must be a 1-D array of integer event columns, not %s of shape %r" % (arr.dtype, arr.shape))
+    if not 1 <= arr.size <= 1 << 24:
+        raise ValueError("cols must hold 1 .. 2^24 event columns, not %d" % arr.size)
+    n_lags = nb + na + 1
+    if n_lags > n:
+        raise ValueError("the window of nb + na + 1 = %d columns is longer than the result's %d" % (n_lags, n))
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    bad = np.flatnonzero((arr < nb) | (arr > n - 1 - na))
+    if bad.size:
+        raise ValueError("cols[%d] = %d: its window of %d columns before and %d after leaves the result's %d columns"
+                         % (bad[0], arr[bad[0]], nb, na, n))
+    pitch = (n_lags + 31) & ~31
+    res = TriggeredResult(None, c, rows, nb, na, pitch, arr.size)
+    nbytes = res.nbytes
+    free, _ = device_memory()
+    if nbytes > free:
+        raise MemoryError("triggered() needs %d bytes on the device for its outputs (%d channels, %d rows, %d lags) "
+                          "and %d are free: fewer rows or a shorter window"
+                          % (nbytes, c, rows[1], n_lags, free))
+    res.buffer = buf = DeviceBuffer(nbytes)
+    ptr = {name: C.c_void_p(buf.ptr.value + off) for name, off in res._offsets().items()}
+    try:
+        check(lib.gcwt_triggered(result.buffer.ptr, result.pitch, c, s, n, rows[0], rows[1],
+                                 arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, nb, na, ptr["amplitude"], ptr["power"],
+                                 ptr["evoked"], ptr["vector"], ptr["itpc"], pitch))
     except Exception:
         res.free()
         raise

@@ -48,6 +48,14 @@ class _Coupling:
         self.time, self.window = time, window
 
 
+class _Triggered:
+    """What ContinuousWaveletTransform.triggered returns (host arrays)."""
+
+    def __init__(self, amplitude, power, evoked, vector, itpc, lags, frequencies, events_used, n_events):
+        self.amplitude, self.power, self.evoked, self.vector, self.itpc = amplitude, power, evoked, vector, itpc
+        self.lags, self.frequencies, self.events_used, self.n_events = lags, frequencies, events_used, n_events
+
+
 class ContinuousWaveletTransform(WaveletTransform):
     """Continuous wavelet transform.
 
@@ -71,6 +79,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         self._coefficients = None
         self._time = None
         self._time_stride = 1               # output_stride of the last transform: time is timestamps[::K]
+        self._stride = 1                    # ... kept after ``time`` has been asked for (triggered(): seconds per column)
         self._plan = None
         self._plan_key = None
         self.last_timings = None
@@ -132,6 +141,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         self.fs = fs                        # validates (transforms.py:109)
         self._time = timestamps
         self._time_stride = stride
+        self._stride = stride
 
         if freqs is not None and freq_limits is not None:
             raise ValueError("freq_limits and freqs cannot both be used at the"
@@ -408,6 +418,56 @@ class ContinuousWaveletTransform(WaveletTransform):
         t = self.time
         return _Coupling(out["mvl"], out["vector"], out["amplitude"], f[phase_rows[0]:phase_rows[0] + phase_rows[1]],
                          f[amp_rows[0]:amp_rows[0] + amp_rows[1]], None if t is None else np.asarray(t)[::window], window)
+
+    def triggered(self, events, *, before, after, freq_limits=None):
+        """Event-locked time-frequency averages of the last transform -- the peri-event spectrogram, the evoked
+        (phase-locked) part and the inter-trial phase coherence --, reduced on the device over the events.  The
+        transform must have been ``output='complex'`` on one device.  ``events``: 1-D event times in seconds on the
+        clock of ``time`` (ripples, stimuli, licks, theta troughs; any order, the order given is the order of the
+        float32 sums); ``before``, ``after``: seconds >= 0 around each event, nb = round(before fs / K) columns and na
+        likewise with the output stride K; ``freq_limits=(lo, hi)``: only the rows whose frequency lies in the closed
+        interval (default: all rows).  An event is dropped when it lies in a gap between epochs or outside the
+        recording, when its window leaves the recording, or when its window would splice two epochs
+        (engine.trigger_columns).  With w_k the coefficient at a lag of event k, E events used and L = nb + na + 1
+        lags, the returned object has ``amplitude`` (C, S', L) float32 = mean |w_k| and ``power`` = mean |w_k|^2 (the
+        peri-event spectrogram, ERSP), ``evoked`` (C, S', L) complex64 = mean w_k (what is phase-locked to the events),
+        ``vector`` (C, S', L) complex64 = mean w_k / |w_k| (its angle: the mean phase), ``itpc`` (C, S', L) float32 =
+        |sum w_k / |w_k|| / E in [0, 1], ``lags`` (L,) seconds = arange(-nb, na + 1) K / fs, ``frequencies`` (S',),
+        ``events_used`` (a bool mask over ``events``) and ``n_events`` = E; after the reference's single-channel call
+        the channel axis is dropped.  The ITPC of E independent phases reads about 0.89 / sqrt(E), not 0 -- a property
+        of the estimator, not an error; no surrogate statistics are made.  A baseline ratio (ERSP in dB) is one NumPy
+        line on the returned arrays: ``10 * np.log10(r.power / r.power[..., r.lags < -0.05].mean(-1, keepdims=True))``.
+        Only the reduced arrays cross to the host; the resident result, ``fetch()`` and the result attributes are
+        untouched."""
+        from .. import engine
+        if self._device_result is None or (self._pending is None and self._last_kind is None):
+            raise ValueError("no transform on the device (call transform() first)")
+        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
+        if out_kind != "complex":
+            raise ValueError("triggered() needs the complex coefficients: the last transform was output='%s', "
+                             "not output='complex'" % out_kind)
+        if not isinstance(self._device_result, engine.DeviceResult):
+            raise ValueError("triggered() works on one device: the last transform was sharded over several "
+                             "(devices=[...]), which is not supported")
+        f = np.array(self._frequencies)
+        rows = (0, f.size) if freq_limits is None else engine.coupling_rows(freq_limits, f, "freq_limits")
+        stride, fs = self._stride, float(self._fs)
+        cols, used, nb, na, why = engine._trigger_scan(events, self.time, fs, stride, before, after,
+                                                       self._device_result.shape[2])
+        if cols.size == 0:
+            raise ValueError("triggered(): none of the %d events can be used: %d lie in a gap between epochs or outside "
+                             "the recording, %d have a window (%d columns before, %d after) that leaves the recording, "
+                             "%d have a window that would splice two epochs"
+                             % (used.size, why["gap"], why["edge"], nb, na, why["splice"]))
+        res = engine.triggered(self._device_result, cols, nb, na, rows)
+        try:
+            out = res.to_host()
+        finally:
+            res.free()
+        if squeeze:
+            out = {k: v[0] for k, v in out.items()}
+        return _Triggered(out["amplitude"], out["power"], out["evoked"], out["vector"], out["itpc"],
+                          np.arange(-nb, na + 1) * stride / fs, f[rows[0]:rows[0] + rows[1]], used, int(cols.size))
 
     def release_device(self):
         """Frees the device copy of the last result (bringing it over first if nothing has asked for it yet)."""

@@ -242,6 +242,32 @@ int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32
 int gcwt_coupling(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   int32_t phase_first, int32_t n_phase, int32_t amp_first, int32_t n_amp, int64_t window,
                   float* d_vector, float* d_mvl, float* d_amplitude, int64_t out_pitch);
+/* Event-locked averages of the rows of a device-resident complex result, on the device that holds it
+ * (csrc/triggered.hip).  d_rows, pitch and n_cols are those of gcwt_coherence; the rows are [row_first, row_first +
+ * n_rows) inside [0, n_scales).  events: n_events (1 .. 2^24 = E) event columns in HOST memory, in any order, repeats
+ * allowed; the entry copies them to the device and frees the copy.  before, after >= 0 columns around an event: L =
+ * before + after + 1 <= n_cols lags, lag l standing for column e_k - before + l, and every event must satisfy before
+ * <= e_k and e_k + after < n_cols.  For every channel c, row r and lag l, with w_k = (re, im) = W[c][r][e_k - before
+ * + l], every operation a single correctly rounded float32 one:
+ *   r2_k = fmaf(im, im, re * re)     a_k = sqrt(r2_k)
+ *   inv_k = a_k > 0 ? 1 / a_k : 0    u_k = (re * inv_k, im * inv_k)
+ *   A = sum a_k    P = sum r2_k    Ev = sum w_k    V = sum u_k
+ *   d_amplitude [C][n_rows][L]  float32    A / E        d_power [C][n_rows][L]   float32    P / E
+ *   d_evoked [C][n_rows][L]     complex64  Ev / E       d_vector [C][n_rows][L]  complex64  V / E
+ *   d_itpc [C][n_rows][L]       float32    min(sqrt(fmaf(V.y, V.y, V.x * V.x)) / E, 1), the inter-trial phase coherence
+ * Every sum is made of four interleaved chains -- chain j adds the terms of the events k = j, j + 4, j + 8, ... one
+ * after the other, from an exact 0 -- combined as (X0 + X1) + (X2 + X3).  The order depends on the event list alone: a
+ * cell (c, r, l) has the same bits alone, inside any larger run of rows, and at the same absolute lag inside any other
+ * (before, after).  Permuting the events changes the chains and with them the low bits.  Zero columns (the gaps between
+ * epochs) add exact zeros.  Any output may be NULL, but not all; their rows are out_pitch (>= L) elements apart.  The
+ * ITPC of E independent phases reads about 0.89 / sqrt(E), not 0: a property of the estimator; no surrogate statistics
+ * are made.  Plan-independent; the device is the one that holds d_rows.  Arguments -- every event among them -- are
+ * checked before any device call (GCWT_ERR_INVALID; the message names the first offending event's index). */
+int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                   int32_t row_first, int32_t n_rows, const int64_t* events, int64_t n_events,
+                   int64_t before, int64_t after,
+                   float* d_amplitude, float* d_power, float* d_evoked, float* d_vector, float* d_itpc,
+                   int64_t out_pitch);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

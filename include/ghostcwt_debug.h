@@ -130,6 +130,16 @@ int gcwt_debug_coupling_grid(int32_t n_channels, int64_t n_cols, int32_t n_phase
                              int32_t* n_phase_tiles, int32_t* n_amp_tiles, int64_t* run_bins, int64_t* n_runs,
                              int64_t* n_blocks);
 
+/* Host only: the grid gcwt_triggered launches for n_rows rows and before + after + 1 lags.  The rows form tiles of
+ * GCWT_TRIGGERED_TILE_ROWS, counted from the first row asked for, and the lags tiles of GCWT_TRIGGERED_TILE_LAGS,
+ * counted from lag 0 (the last tile of either may be ragged); a workgroup takes one (channel, lag tile, row tile) and
+ * every event.  n_blocks counts the workgroups: every row tile of every (channel, lag tile), the (channel, lag tile)s
+ * padded to a multiple of 8 so that the row tiles of one of them lie 8 workgroups apart.  Any pointer may be NULL.
+ * Returns GCWT_OK or an error code < 0 (a grid of more than 2^31 - 1 workgroups among them). */
+enum { GCWT_TRIGGERED_TILE_ROWS = 4, GCWT_TRIGGERED_TILE_LAGS = 64 };
+int gcwt_debug_triggered_grid(int32_t n_channels, int32_t n_rows, int64_t before, int64_t after, int32_t* n_row_tiles,
+                              int64_t* n_lag_tiles, int64_t* n_blocks);
+
 #ifdef __cplusplus
 }
 #endif
