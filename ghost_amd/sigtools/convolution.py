@@ -41,13 +41,25 @@ def _check_mode(mode, n, m):
     return mode
 
 
+def _grid_log2(n, m, fft_length):
+    """log2 of the plan's FFT for the reference's ``fft_length``: rounded up to a power of two of at
+    least 4096, then doubled while gcwt_conv_plan_create would refuse it (chunks of fewer than
+    P / 8 new samples, when the convolution does not fit one chunk) and 2^22 is not reached."""
+    log2 = max(12, (fft_length - 1).bit_length())
+    while log2 < 22 and n + m - 1 > (1 << log2) and (1 << log2) - (m - 1) < (1 << log2) // 8:
+        log2 += 1
+    return log2
+
+
 class ConvPlan:
     """Convolution of ``n_channels`` real signals of ``n_samples`` with one kernel of
     ``kernel_len`` taps.  ``fft_length``: None (the smallest power of two that holds the
     whole convolution as one overlap-save chunk, ``n + 2 (m - 1)`` points, at most 2^22; longer
     signals are chunked) or the reference's ``fft_length`` (chunks of ``fft_length - kernel_len + 1``):
     any value up to 2^22 is taken and rounded UP to a power of two of at least 4096 (the
-    reference accepts any length; the result does not depend on it)."""
+    reference accepts any length; the result does not depend on it).  A grid that would leave a
+    chunked signal fewer than ``fft_length / 8`` new samples per chunk (a kernel nearly as long
+    as the FFT, which the library refuses) is doubled until it does not; ``fft_length`` tells."""
 
     def __init__(self, n_samples, kernel_len, n_channels=1, *, fft_length=None, device=-1):
         self._handle = _vp()
@@ -55,7 +67,7 @@ class ConvPlan:
         if fft_length is not None:
             if int(fft_length) < 1 or int(fft_length) > (1 << 22):
                 raise ValueError("fft_length must be between 1 and 2**22")
-            log2 = max(12, (int(fft_length) - 1).bit_length())      # rounded up to a power of two >= 4096
+            log2 = _grid_log2(int(n_samples), int(kernel_len), int(fft_length))
         check(lib.gcwt_conv_plan_create(C.byref(self._handle), int(n_samples), int(kernel_len),
                                         int(n_channels), log2, int(device)))
         self.n_samples, self.kernel_len, self.n_channels = int(n_samples), int(kernel_len), int(n_channels)
@@ -189,10 +201,10 @@ def fastconv_hip(signal, kernel, *, mode=None, fft_length=None, device=-1, preci
 def fastconv_freq_hip(signal_td, kernel_fd, kernel_len, *, mode=None, device=-1, precision=None):
     """Convolution with a kernel given by its DFT (any length >= ``kernel_len``), as
     ``fastconv_freq_scipy(signal_td, kernel_fd, kernel_len, mode=...)``.  When the DFT is
-    on a power-of-two grid the plan can take (4096 .. 2^22 bins) it is used as it is and the
-    signal is chunked exactly as the reference does (``len(kernel_fd) - kernel_len + 1``
-    samples per chunk, convolution.py:262); any other grid goes back to the time domain on
-    the host first (the kernel is short)."""
+    on a power-of-two grid the plan can take (4096 .. 2^22 bins, at least an eighth of them new
+    samples per chunk) it is used as it is and the signal is chunked exactly as the reference
+    does (``len(kernel_fd) - kernel_len + 1`` samples per chunk, convolution.py:262); any
+    other grid goes back to the time domain on the host first (the kernel is short)."""
     signal_td = np.asarray(signal_td)
     kernel_fd = np.asarray(kernel_fd)
     if signal_td.ndim != 1:
@@ -207,7 +219,7 @@ def fastconv_freq_hip(signal_td, kernel_fd, kernel_len, *, mode=None, device=-1,
         kernel_td = _dft(np.asarray(kernel_fd, dtype=np.complex128), True, device, "high")[:m]
         herm = np.abs(kernel_fd[1:] - np.conj(kernel_fd[:0:-1])).max() <= 1e-12 * np.abs(kernel_fd).max() if f > 1 else True
         return _fastconv_f64(signal_td, kernel_td.real.copy() if herm else kernel_td, mode, device)
-    if f >= 4096 and f <= (1 << 22) and (f & (f - 1)) == 0 and f >= m:
+    if f >= 4096 and f <= (1 << 22) and (f & (f - 1)) == 0 and f >= m and (1 << _grid_log2(n, m, f)) == f:
         # real taps <=> Hermitian spectrum: hand back float32 like fastconv_hip does
         herm = np.abs(kernel_fd[1:] - np.conj(kernel_fd[:0:-1])).max() <= 1e-6 * np.abs(kernel_fd).max()
         plan = _plan_for(n, m, f, int(device))
