@@ -17,6 +17,7 @@
 #include "../../include/ghostcwt_debug.h"
 #include <memory>
 
+#include "errors.h"
 #include "host_out.h"
 #include "interp.h"
 #include "kernels.h"
@@ -40,20 +41,6 @@ int set_err(int code, const std::string& msg) {
 int hip_err(hipError_t e, const char* what) {
   g_err = std::string(what) + ": " + hipGetErrorString(e);
   return e == hipErrorOutOfMemory ? GCWT_ERR_NOMEM : GCWT_ERR_HIP;
-}
-
-// Nothing may unwind across the C ABI: entry points that allocate run inside this.
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return set_err(GCWT_ERR_NOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return set_err(GCWT_ERR_INVALID, std::string("internal error: ") + e.what());
-  } catch (...) {
-    return set_err(GCWT_ERR_INVALID, "internal error");
-  }
 }
 
 #define HIP_TRY(call)                                  \

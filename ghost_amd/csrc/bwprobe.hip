@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/ghostcwt_debug.h"
+#include "errors.h"
 
 namespace {
 
@@ -88,8 +89,6 @@ __global__ void __launch_bounds__(256) k_check_rows(const uint32_t* __restrict__
 }
 
 }  // namespace
-
-int gcwt_internal_set_error(int code, const char* msg);
 
 extern "C" int gcwt_debug_check_output(const void* out_device, int64_t row_pitch_floats, int64_t n_valid_floats,
                                        int32_t rows_per_channel, int32_t n_channels, int32_t distinct,

@@ -4,15 +4,13 @@
 
 #include <algorithm>
 #include <map>
-#include <new>
 #include <string>
 #include <utility>
 
-#include "../../include/ghostcwt.h"
 #include "../../include/ghostcwt_debug.h"
 #include "coherence.h"
-
-int gcwt_internal_set_error(int code, const char* msg);   // api.cpp (C++ linkage)
+#include "errors.h"
+#include "resident_op.h"
 
 static_assert(gcwt::kCohTile == GCWT_COHERENCE_TILE, "ghostcwt_debug.h names the tile the kernel is built for");
 
@@ -67,24 +65,15 @@ void coherence_tasks(int32_t n_channels, const int32_t* pairs, int32_t n_pairs, 
 
 }  // namespace gcwt
 
+using namespace gcwt;
+
 namespace {
 
-int fail(int code, const std::string& m) { return gcwt_internal_set_error(code, m.c_str()); }
-
-// nothing may unwind across the C ABI
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(GCWT_ERR_NOMEM, "out of host memory");
-  } catch (...) {
-    return fail(GCWT_ERR_INVALID, "internal error");
-  }
-}
+constexpr const char* kOp = "gcwt_coherence";
 
 int check_pairs(int32_t n_channels, const int32_t* pairs, int32_t n_pairs) {
-  if (n_channels < 1) return fail(GCWT_ERR_INVALID, "gcwt_coherence: n_channels must be at least 1");
+  const int rc = check_channels(kOp, n_channels);
+  if (rc) return rc;
   if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return fail(GCWT_ERR_INVALID, "gcwt_coherence: pairs is NULL or n_pairs negative");
   for (int32_t p = 0; p < n_pairs; ++p) {
     const int32_t a = pairs[2 * p], b = pairs[2 * p + 1];
@@ -94,11 +83,6 @@ int check_pairs(int32_t n_channels, const int32_t* pairs, int32_t n_pairs) {
   }
   return GCWT_OK;
 }
-
-struct DeviceTables {
-  void* p = nullptr;
-  ~DeviceTables() { if (p) (void)hipFree(p); }
-};
 
 }  // namespace
 
@@ -135,36 +119,19 @@ int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32
                    float* d_coherence, int64_t out_pitch) {
   return guarded([&] {
     if (!d_rows) return fail(GCWT_ERR_INVALID, "gcwt_coherence: d_rows is NULL");
-    if (n_scales < 1 || n_cols < 1 || pitch < n_cols)
-      return fail(GCWT_ERR_INVALID, "gcwt_coherence: bad rows (n_scales, n_cols >= 1, pitch >= n_cols)");
-    if (window < 2) return fail(GCWT_ERR_INVALID, "gcwt_coherence: window must be at least 2 columns");
-    int rc = check_pairs(n_channels, pairs, n_pairs);
+    int rc = check_rows(kOp, n_scales, n_cols, pitch);
+    if (rc) return rc;
+    rc = check_window(kOp, window);
+    if (rc) return rc;
+    rc = check_pairs(n_channels, pairs, n_pairs);
     if (rc) return rc;
     if (!d_power && (n_pairs == 0 || (!d_cross && !d_coherence)))
       return fail(GCWT_ERR_INVALID, "gcwt_coherence: nothing to compute (no output, or no pairs and no d_power)");
     const int64_t n_bins = (n_cols + window - 1) / window;
     if (out_pitch < n_bins) return fail(GCWT_ERR_INVALID, "gcwt_coherence: out_pitch is below the number of bins, ceil(n_cols / window)");
 
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_NO_DEVICE, "no HIP device: libghostcwt has no CPU path");
-    }
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_rows) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_INVALID, "gcwt_coherence: d_rows is not device memory");
-    }
-    const int device = attr.device;
-    for (const void* out : {(const void*)d_power, (const void*)d_cross, (const void*)d_coherence}) {
-      if (!out) continue;
-      if (hipPointerGetAttributes(&attr, out) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) {
-        (void)hipGetLastError();
-        return fail(GCWT_ERR_INVALID, "gcwt_coherence: an output is not memory of the device that holds d_rows");
-      }
-    }
-    hipError_t e = hipSetDevice(device);                   // (the calling thread's device, from here on)
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = resolve_device(kOp, d_rows, {d_power, d_cross, d_coherence});
+    if (rc) return rc;
 
     std::vector<gcwt::CohTask> tasks;
     std::vector<gcwt::CohEntry> ent;
@@ -180,12 +147,11 @@ int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32
 
     const size_t task_bytes = sizeof(gcwt::CohTask) * tasks.size();
     const size_t ent_bytes = sizeof(gcwt::CohEntry) * std::max<size_t>(1, ent.size());
-    DeviceTables tab;
-    e = hipMalloc(&tab.p, task_bytes + ent_bytes);
+    DeviceCopy tab;
+    hipError_t e = tab.alloc(task_bytes + ent_bytes);
     if (e != hipSuccess) return fail(GCWT_ERR_NOMEM, std::string("gcwt_coherence: ") + hipGetErrorString(e));
-    e = hipMemcpy(tab.p, tasks.data(), task_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !ent.empty())
-      e = hipMemcpy((char*)tab.p + task_bytes, ent.data(), sizeof(gcwt::CohEntry) * ent.size(), hipMemcpyHostToDevice);
+    e = tab.put(0, tasks.data(), task_bytes);
+    if (e == hipSuccess && !ent.empty()) e = tab.put(task_bytes, ent.data(), sizeof(gcwt::CohEntry) * ent.size());
     if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coherence: ") + hipGetErrorString(e));
 
     gcwt::CohArgs a{};

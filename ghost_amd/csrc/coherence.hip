@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "coherence.h"
+#include "wave_reduce.h"
 
 namespace gcwt {
 
@@ -30,21 +31,6 @@ namespace {
 
 constexpr int kWaves = 4;                                   // per workgroup; each takes every fourth bin of the run
 constexpr int kRedFloats = 2 * kCohCells + 2 * kCohTile;    // a wave's reduced sums: (re, im) per cell, Sxx per row of A, of B
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// the fixed tree: every lane returns the sum over the wave
-__device__ __forceinline__ float wave_sum(float v) {
-  v = __fadd_rn(v, dpp<0xB1>(v));        // quad_perm [1, 0, 3, 2]: lane ^ 1
-  v = __fadd_rn(v, dpp<0x4E>(v));        // quad_perm [2, 3, 0, 1]: lane ^ 2
-  v = __fadd_rn(v, dpp<0x141>(v));       // row_half_mirror: the other quad of the 8 (quads are uniform by now)
-  v = __fadd_rn(v, dpp<0x140>(v));       // row_mirror: the other 8 of the 16
-  v = __fadd_rn(v, __shfl_xor(v, 16));
-  v = __fadd_rn(v, __shfl_xor(v, 32));
-  return v;
-}
 
 template <bool ALL>
 __device__ __forceinline__ void run_task(const CohArgs& a, const CohTask& tk, int s, int64_t run, float* red) {
@@ -89,8 +75,8 @@ __device__ __forceinline__ void run_task(const CohArgs& a, const CohTask& tk, in
       }
 #pragma unroll
       for (int i = 0; i < kCohTile; ++i) {
-        if ((rows_a >> i) & 1) pa[i] = __fadd_rn(pa[i], fmaf(va[i].y, va[i].y, __fmul_rn(va[i].x, va[i].x)));
-        if ((rows_b >> i) & 1) pb[i] = __fadd_rn(pb[i], fmaf(vb[i].y, vb[i].y, __fmul_rn(vb[i].x, vb[i].x)));
+        if ((rows_a >> i) & 1) pa[i] = __fadd_rn(pa[i], norm2(va[i]));
+        if ((rows_b >> i) & 1) pb[i] = __fadd_rn(pb[i], norm2(vb[i]));
       }
 #pragma unroll
       for (int i = 0; i < kCohTile; ++i) {
@@ -126,9 +112,7 @@ __device__ __forceinline__ void run_task(const CohArgs& a, const CohTask& tk, in
         if (lane == 0) red[2 * kCohCells + kCohTile + k] = r;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const float cnt = (float)(c_end - c_begin);
     for (int e = lane; e < tk.n_entries; e += 64) {
@@ -150,9 +134,7 @@ __device__ __forceinline__ void run_task(const CohArgs& a, const CohTask& tk, in
         a.power[(ch * a.n_scales + s) * a.out_pitch + m] = red[2 * kCohCells + lane] / cnt;
     }
     // (the next bin's sums go to the same piece of LDS: not before these reads)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 }
 

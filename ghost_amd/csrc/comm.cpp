@@ -12,7 +12,7 @@
 #include <new>
 #include <string>
 
-#include "../../include/ghostcwt.h"
+#include "errors.h"
 
 // minimal RCCL surface (matches rccl.h / nccl.h ABI)
 typedef struct ncclComm* ncclComm_t;
@@ -84,23 +84,22 @@ struct gcwt_comm {
 
 // errors from this file are reported through the same gcwt_last_error() string
 extern "C" const char* gcwt_last_error(void);
-int gcwt_internal_set_error(int code, const char* msg);
 
 namespace {
-int cerr_(int code, const std::string& m) { return gcwt_internal_set_error(code, m.c_str()); }
+using gcwt::fail;
 int nccl_fail(const char* what, ncclResult_t r) {
   std::string m = std::string(what) + ": ";
   m += rccl().GetErrorString ? rccl().GetErrorString(r) : "RCCL error";
-  return cerr_(GCWT_ERR_COMM, m);
+  return fail(GCWT_ERR_COMM, m);
 }
 }  // namespace
 
 extern "C" {
 
 int gcwt_comm_unique_id(void* id128) {
-  if (!id128) return cerr_(GCWT_ERR_INVALID, "NULL id buffer");
+  if (!id128) return fail(GCWT_ERR_INVALID, "NULL id buffer");
   Rccl& r = rccl();
-  if (!r.ok) return cerr_(GCWT_ERR_COMM, "librccl not found or incomplete");
+  if (!r.ok) return fail(GCWT_ERR_COMM, "librccl not found or incomplete");
   ncclUniqueId id;
   ncclResult_t rc;
   rc = r.GetUniqueId(&id);
@@ -112,18 +111,18 @@ int gcwt_comm_unique_id(void* id128) {
 
 int gcwt_comm_create(gcwt_comm** out, int rank, int n_ranks, const void* id128) {
   if (!out || !id128 || n_ranks < 1 || rank < 0 || rank >= n_ranks)
-    return cerr_(GCWT_ERR_INVALID, "bad communicator arguments");
+    return fail(GCWT_ERR_INVALID, "bad communicator arguments");
   *out = nullptr;
   Rccl& r = rccl();
-  if (!r.ok) return cerr_(GCWT_ERR_COMM, "librccl not found or incomplete");
+  if (!r.ok) return fail(GCWT_ERR_COMM, "librccl not found or incomplete");
   gcwt_comm* c = new (std::nothrow) gcwt_comm();
-  if (!c) return cerr_(GCWT_ERR_NOMEM, "out of host memory");
+  if (!c) return fail(GCWT_ERR_NOMEM, "out of host memory");
   // ncclCommInitRank binds the communicator to the calling thread's current device: take note of it (and make
   // sure there is one: without a device this is the caller's error, not RCCL's)
   if (hipGetDevice(&c->device) != hipSuccess || hipSetDevice(c->device) != hipSuccess) {
     (void)hipGetLastError();
     delete c;
-    return cerr_(GCWT_ERR_NO_DEVICE, "no current HIP device for the communicator (gcwt_set_device first)");
+    return fail(GCWT_ERR_NO_DEVICE, "no current HIP device for the communicator (gcwt_set_device first)");
   }
   c->rank = rank;
   c->n_ranks = n_ranks;
@@ -136,7 +135,7 @@ int gcwt_comm_create(gcwt_comm** out, int rank, int n_ranks, const void* id128) 
       hipMalloc((void**)&c->d_val, sizeof(double)) != hipSuccess) {
     r.CommDestroy(c->comm);
     delete c;
-    return cerr_(GCWT_ERR_HIP, "communicator scratch allocation failed");
+    return fail(GCWT_ERR_HIP, "communicator scratch allocation failed");
   }
   *out = c;
   return GCWT_OK;
@@ -165,16 +164,16 @@ void gcwt_comm_abort(gcwt_comm* c) {
 }
 
 int gcwt_comm_allreduce_max(gcwt_comm* c, double* value) {
-  if (!c || !value) return cerr_(GCWT_ERR_INVALID, "NULL argument");
-  if (hipSetDevice(c->device) != hipSuccess) return cerr_(GCWT_ERR_HIP, "the communicator's device cannot be selected");
+  if (!c || !value) return fail(GCWT_ERR_INVALID, "NULL argument");
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GCWT_ERR_HIP, "the communicator's device cannot be selected");
   if (hipMemcpyAsync(c->d_val, value, sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return cerr_(GCWT_ERR_HIP, "copy to device failed");
+    return fail(GCWT_ERR_HIP, "copy to device failed");
   ncclResult_t rc;
   rc = rccl().AllReduce(c->d_val, c->d_val, 1, kNcclFloat64, kNcclMax, c->comm, c->stream);
   if (rc != 0) return nccl_fail("ncclAllReduce", rc);
   if (hipMemcpyAsync(value, c->d_val, sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
-    return cerr_(GCWT_ERR_COMM_INCOMPLETE, "all-reduce was enqueued and did not complete");
+    return fail(GCWT_ERR_COMM_INCOMPLETE, "all-reduce was enqueued and did not complete");
   return GCWT_OK;
 }
 
@@ -184,7 +183,7 @@ int gcwt_comm_barrier(gcwt_comm* c) {
 }
 
 int gcwt_comm_broadcast_bank(gcwt_comm* c, gcwt_plan* plan, int root) {
-  if (!c || !plan) return cerr_(GCWT_ERR_INVALID, "NULL argument");
+  if (!c || !plan) return fail(GCWT_ERR_INVALID, "NULL argument");
   int rc = gcwt_plan_upload(plan);
   if (rc) return rc;
   // the plan's bank lives on the plan's device; the communicator must have been made on the same one
@@ -192,14 +191,14 @@ int gcwt_comm_broadcast_bank(gcwt_comm* c, gcwt_plan* plan, int root) {
   size_t bytes = 0;
   float2* bank = gcwt_internal_bank_ptr(plan, &bytes);
   if (hipPointerGetAttributes(&attr, bank) == hipSuccess && attr.device != c->device)
-    return cerr_(GCWT_ERR_INVALID, "the plan and the communicator are on different devices");
-  if (hipSetDevice(c->device) != hipSuccess) return cerr_(GCWT_ERR_HIP, "the communicator's device cannot be selected");
+    return fail(GCWT_ERR_INVALID, "the plan and the communicator are on different devices");
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GCWT_ERR_HIP, "the communicator's device cannot be selected");
   hipStream_t st = gcwt_internal_stream(plan);
   const ncclResult_t nr = rccl().Broadcast(bank, bank, bytes, kNcclUint8, root, c->comm, st);
   if (nr != 0) return nccl_fail("ncclBroadcast", nr);
   if ((rc = gcwt_internal_refresh_bank(plan))) return rc;   // signed gain table follows the bank
   if (hipStreamSynchronize(st) != hipSuccess)
-    return cerr_(GCWT_ERR_COMM_INCOMPLETE, "broadcast was enqueued and did not complete");
+    return fail(GCWT_ERR_COMM_INCOMPLETE, "broadcast was enqueued and did not complete");
   return GCWT_OK;
 }
 

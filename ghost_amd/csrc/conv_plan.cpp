@@ -17,13 +17,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ghostcwt.h"
+#include "errors.h"
 #include "kernels.h"
 #include "planner.h"
 
 using namespace gcwt;
-
-int gcwt_internal_set_error(int code, const char* msg);   // api.cpp (C++ linkage)
 
 struct gcwt_conv_plan {
   int64_t n = 0, m = 0, p = 0, step = 0, n_chunks = 0;
@@ -40,7 +38,6 @@ struct gcwt_conv_plan {
 
 namespace {
 
-int fail(int code, const std::string& msg) { return gcwt_internal_set_error(code, msg.c_str()); }
 int hip_fail(hipError_t e, const char* what) {
   return fail(e == hipErrorOutOfMemory ? GCWT_ERR_NOMEM : GCWT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }

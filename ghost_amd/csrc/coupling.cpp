@@ -3,45 +3,31 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 #include <string>
 
-#include "../../include/ghostcwt.h"
 #include "../../include/ghostcwt_debug.h"
 #include "coupling.h"
-
-int gcwt_internal_set_error(int code, const char* msg);   // api.cpp (C++ linkage)
+#include "errors.h"
+#include "resident_op.h"
 
 static_assert(gcwt::kCplPhase == GCWT_COUPLING_TILE_PHASE && gcwt::kCplAmp == GCWT_COUPLING_TILE_AMP,
               "ghostcwt_debug.h names the tile the kernel is built for");
 
+using namespace gcwt;
+
 namespace {
 
-int fail(int code, const std::string& m) { return gcwt_internal_set_error(code, m.c_str()); }
-
-// nothing may unwind across the C ABI
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(GCWT_ERR_NOMEM, "out of host memory");
-  } catch (...) {
-    return fail(GCWT_ERR_INVALID, "internal error");
-  }
-}
+constexpr const char* kOp = "gcwt_coupling";
 
 // everything that needs no device; fills the grid's numbers
 int check_and_cut(int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols, int32_t phase_first,
                   int32_t n_phase, int32_t amp_first, int32_t n_amp, int64_t window, gcwt::CplArgs* a) {
-  if (n_channels < 1) return fail(GCWT_ERR_INVALID, "gcwt_coupling: n_channels must be at least 1");
-  if (n_scales < 1 || n_cols < 1 || pitch < n_cols)
-    return fail(GCWT_ERR_INVALID, "gcwt_coupling: bad rows (n_scales, n_cols >= 1, pitch >= n_cols)");
-  if (window < 2) return fail(GCWT_ERR_INVALID, "gcwt_coupling: window must be at least 2 columns");
-  if (phase_first < 0 || n_phase < 1 || n_phase > n_scales - phase_first)
-    return fail(GCWT_ERR_INVALID, "gcwt_coupling: the phase rows must be a non-empty range inside [0, n_scales)");
-  if (amp_first < 0 || n_amp < 1 || n_amp > n_scales - amp_first)
-    return fail(GCWT_ERR_INVALID, "gcwt_coupling: the amplitude rows must be a non-empty range inside [0, n_scales)");
+  int rc = check_channels(kOp, n_channels);
+  if (!rc) rc = check_rows(kOp, n_scales, n_cols, pitch);
+  if (!rc) rc = check_window(kOp, window);
+  if (!rc) rc = check_row_range(kOp, "phase rows", phase_first, n_phase, n_scales);
+  if (!rc) rc = check_row_range(kOp, "amplitude rows", amp_first, n_amp, n_scales);
+  if (rc) return rc;
   a->pitch = pitch; a->n_cols = n_cols; a->window = window;
   a->n_bins = (n_cols + window - 1) / window;
   a->n_channels = n_channels; a->n_scales = n_scales;
@@ -86,36 +72,18 @@ int gcwt_coupling(const float* d_rows, int64_t pitch, int32_t n_channels, int32_
   return guarded([&] {
     if (!d_rows) return fail(GCWT_ERR_INVALID, "gcwt_coupling: d_rows is NULL");
     gcwt::CplArgs a{};
-    const int rc = check_and_cut(pitch, n_channels, n_scales, n_cols, phase_first, n_phase, amp_first, n_amp, window, &a);
+    int rc = check_and_cut(pitch, n_channels, n_scales, n_cols, phase_first, n_phase, amp_first, n_amp, window, &a);
     if (rc) return rc;
     if (!d_vector && !d_mvl && !d_amplitude) return fail(GCWT_ERR_INVALID, "gcwt_coupling: nothing to compute (no output)");
     if (out_pitch < a.n_bins) return fail(GCWT_ERR_INVALID, "gcwt_coupling: out_pitch is below the number of bins, ceil(n_cols / window)");
 
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_NO_DEVICE, "no HIP device: libghostcwt has no CPU path");
-    }
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_rows) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_INVALID, "gcwt_coupling: d_rows is not device memory");
-    }
-    const int device = attr.device;
-    for (const void* out : {(const void*)d_vector, (const void*)d_mvl, (const void*)d_amplitude}) {
-      if (!out) continue;
-      if (hipPointerGetAttributes(&attr, out) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) {
-        (void)hipGetLastError();
-        return fail(GCWT_ERR_INVALID, "gcwt_coupling: an output is not memory of the device that holds d_rows");
-      }
-    }
-    hipError_t e = hipSetDevice(device);                   // (the calling thread's device, from here on)
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = resolve_device(kOp, d_rows, {d_vector, d_mvl, d_amplitude});
+    if (rc) return rc;
 
     a.rows = reinterpret_cast<const float2*>(d_rows);
     a.out_pitch = out_pitch;
     a.vector = reinterpret_cast<float2*>(d_vector); a.mvl = d_mvl; a.amplitude = d_amplitude;
-    e = gcwt::launch_coupling(a, nullptr);
+    hipError_t e = gcwt::launch_coupling(a, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coupling: ") + hipGetErrorString(e));
     return (int)GCWT_OK;

@@ -7,12 +7,13 @@
 
 #include <cstdint>
 
+#include "resident_op.h"
+
 namespace gcwt {
 
 constexpr int kCplPhase = 4;                      // phase rows per tile
 constexpr int kCplAmp = 8;                        // amplitude rows per tile
 constexpr int kCplCells = kCplPhase * kCplAmp;    // cell (i, j) = i * kCplAmp + j: 64 accumulators (re, im) and 8 for S
-constexpr int kCplShare = 8;                      // workgroups b and b + kCplShare share an L2 (coupling.hip: the grid)
 
 struct CplArgs {
   const float2* rows;          // [channel][scale] rows, pitch complex elements apart
@@ -22,10 +23,8 @@ struct CplArgs {
   float* mvl;                  // [C][P][A][out_pitch] or NULL
   float* amplitude;            // [C][A][out_pitch] or NULL
 };
-// workgroups of the grid: every (unit, tile), units padded to a multiple of kCplShare
-inline int64_t coupling_blocks(const CplArgs& a) {
-  return (a.n_units + kCplShare - 1) / kCplShare * kCplShare * a.n_ptiles * a.n_atiles;
-}
+// workgroups of the grid: the tiles of a unit share its rows (resident_op.h: the placement)
+inline int64_t coupling_blocks(const CplArgs& a) { return shared_blocks(a.n_units, (int64_t)a.n_ptiles * a.n_atiles); }
 hipError_t launch_coupling(const CplArgs& a, hipStream_t st);
 
 }  // namespace gcwt

@@ -22,9 +22,8 @@
 // row alone and |w| on its amplitude row alone, so a cell (p, a) asked for alone and the same cell inside any larger
 // ranges run the same instructions on the same numbers: the same bits.
 //
-// The grid: workgroups b and b + 8 are dealt to the same XCD, so the tiles of one (channel, run) -- which read the same
-// rows -- are placed 8 apart: index = (group of 8 units, tile, unit in the group).  They start together and meet their
-// rows in one L2.  This is for speed only; nothing depends on the placement.
+// The grid: the tiles of one (channel, run) read the same rows and are placed to meet them in one L2 (resident_op.h:
+// the placement).  This is for speed only; nothing depends on it.
 //
 // Loads are 8 bytes per lane -- one complex column, 512 contiguous bytes of a row per wave and load -- for the reason
 // coherence.hip gives: a 16-byte load would change a lane's chain.
@@ -33,6 +32,7 @@
 #include <algorithm>
 
 #include "coupling.h"
+#include "wave_reduce.h"
 
 namespace gcwt {
 
@@ -40,26 +40,6 @@ namespace {
 
 constexpr int kWaves = 4;                                   // per workgroup; each takes every fourth bin of the run
 constexpr int kRedFloats = 2 * kCplCells + kCplAmp;         // a wave's reduced sums: (re, im) per cell, S per amplitude row
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// the fixed tree of coherence.hip: every lane returns the sum over the wave
-__device__ __forceinline__ float wave_sum(float v) {
-  v = __fadd_rn(v, dpp<0xB1>(v));        // quad_perm [1, 0, 3, 2]: lane ^ 1
-  v = __fadd_rn(v, dpp<0x4E>(v));        // quad_perm [2, 3, 0, 1]: lane ^ 2
-  v = __fadd_rn(v, dpp<0x141>(v));       // row_half_mirror: the other quad of the 8 (quads are uniform by now)
-  v = __fadd_rn(v, dpp<0x140>(v));       // row_mirror: the other 8 of the 16
-  v = __fadd_rn(v, __shfl_xor(v, 16));
-  v = __fadd_rn(v, __shfl_xor(v, 32));
-  return v;
-}
-
-// |w| as prescribed: two roundings in r2, one in the root
-__device__ __forceinline__ float modulus(float2 v) {
-  return __builtin_sqrtf(fmaf(v.y, v.y, __fmul_rn(v.x, v.x)));
-}
 
 // FULL: all kCplPhase x kCplAmp rows exist (no row tests in the column loop)
 template <bool FULL>
@@ -133,9 +113,7 @@ __device__ __forceinline__ void run_tile(const CplArgs& a, int ch, int tp, int t
       const float r = wave_sum(sa[k]);
       if (lane == 0) red[2 * kCplCells + k] = r;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     const float cnt = (float)(c_end - c_begin);
     if (lane < kCplCells) {                                  // lane = cell
@@ -144,30 +122,23 @@ __device__ __forceinline__ void run_tile(const CplArgs& a, int ch, int tp, int t
         const float r = red[2 * lane], q = red[2 * lane + 1], s = red[2 * kCplCells + j];
         const int64_t o = (((int64_t)ch * a.n_phase + tp * kCplPhase + i) * a.n_amp + ta * kCplAmp + j) * a.out_pitch + m;
         if (a.vector) a.vector[o] = make_float2(r / cnt, q / cnt);
-        if (a.mvl) a.mvl[o] = s > 0.f ? fminf(__builtin_sqrtf(fmaf(q, q, __fmul_rn(r, r))) / s, 1.f) : 0.f;
+        if (a.mvl) a.mvl[o] = s > 0.f ? fminf(modulus(make_float2(r, q)) / s, 1.f) : 0.f;
       }
     }
     if (a.amplitude && tp == 0 && lane < n_a)                // the first phase tile writes the amplitude rows
       a.amplitude[((int64_t)ch * a.n_amp + ta * kCplAmp + lane) * a.out_pitch + m] = red[2 * kCplCells + lane] / cnt;
     // (the next bin's sums go to the same piece of LDS: not before these reads)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 }
 
 __global__ void __launch_bounds__(64 * kWaves, 3) k_coupling(CplArgs a) {
   __shared__ float s_red[kWaves][kRedFloats];
-  const int n_tiles = a.n_ptiles * a.n_atiles;
-  int64_t idx = blockIdx.x;                                  // (group of kCplShare units, tile, unit in the group)
-  const int member = (int)(idx % kCplShare);
-  idx /= kCplShare;
-  const int tile = (int)(idx % n_tiles);
-  const int64_t unit = idx / n_tiles * kCplShare + member;
-  if (unit >= a.n_units) return;                             // (the last group's padding)
-  const int ch = (int)(unit / a.n_runs);
-  const int64_t run = unit % a.n_runs;
-  const int tp = tile / a.n_atiles, ta = tile % a.n_atiles;
+  const TileOfUnit at = shared_place(a.n_ptiles * a.n_atiles);   // unit = (channel, run)
+  if (at.unit >= a.n_units) return;                          // (the last group's padding)
+  const int ch = (int)(at.unit / a.n_runs);
+  const int64_t run = at.unit % a.n_runs;
+  const int tp = at.tile / a.n_atiles, ta = at.tile % a.n_atiles;
   float* red = s_red[threadIdx.x >> 6];
   if ((tp + 1) * kCplPhase <= a.n_phase && (ta + 1) * kCplAmp <= a.n_amp)
     run_tile<true>(a, ch, tp, ta, run, red);

@@ -1,0 +1,71 @@
+// resident_op.cpp -- the host side every row operator shares (resident_op.h).
+#include "resident_op.h"
+
+#include <string>
+
+#include "errors.h"
+
+namespace gcwt {
+
+int check_channels(const char* op, int32_t n_channels) {
+  if (n_channels < 1) return fail(GCWT_ERR_INVALID, std::string(op) + ": n_channels must be at least 1");
+  return GCWT_OK;
+}
+
+int check_rows(const char* op, int32_t n_scales, int64_t n_cols, int64_t pitch) {
+  if (n_scales < 1 || n_cols < 1 || pitch < n_cols)
+    return fail(GCWT_ERR_INVALID, std::string(op) + ": bad rows (n_scales, n_cols >= 1, pitch >= n_cols)");
+  return GCWT_OK;
+}
+
+int check_window(const char* op, int64_t window) {
+  if (window < 2) return fail(GCWT_ERR_INVALID, std::string(op) + ": window must be at least 2 columns");
+  return GCWT_OK;
+}
+
+int check_row_range(const char* op, const char* noun, int32_t first, int32_t count, int32_t n_scales) {
+  if (first < 0 || count < 1 || count > n_scales - first)
+    return fail(GCWT_ERR_INVALID, std::string(op) + ": the " + noun + " must be a non-empty range inside [0, n_scales)");
+  return GCWT_OK;
+}
+
+int resolve_device(const char* op, const void* d_rows, std::initializer_list<const void*> outputs) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
+    (void)hipGetLastError();
+    return fail(GCWT_ERR_NO_DEVICE, "no HIP device: libghostcwt has no CPU path");
+  }
+  auto device_of = [](const void* p) {                     // -1: not device memory
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice) return attr.device;
+    (void)hipGetLastError();
+    return -1;
+  };
+  const int device = device_of(d_rows);
+  if (device < 0) return fail(GCWT_ERR_INVALID, std::string(op) + ": d_rows is not device memory");
+  for (const void* out : outputs)
+    if (out && device_of(out) != device)
+      return fail(GCWT_ERR_INVALID, std::string(op) + ": an output is not memory of the device that holds d_rows");
+  const hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  return GCWT_OK;
+}
+
+DeviceCopy::~DeviceCopy() {
+  if (p) (void)hipFree(p);
+}
+
+hipError_t DeviceCopy::alloc(size_t bytes) {
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    p = nullptr;
+    (void)hipGetLastError();
+  }
+  return e;
+}
+
+hipError_t DeviceCopy::put(size_t offset, const void* host, size_t bytes) {
+  return hipMemcpy(static_cast<char*>(p) + offset, host, bytes, hipMemcpyHostToDevice);
+}
+
+}  // namespace gcwt

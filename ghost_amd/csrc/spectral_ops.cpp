@@ -9,17 +9,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ghostcwt.h"
+#include "errors.h"
 #include "kernels.h"
 #include "planner.h"
 
 using namespace gcwt;
 
-int gcwt_internal_set_error(int code, const char* msg);   // api.cpp (C++ linkage)
-
 namespace {
-
-int fail(int code, const std::string& m) { return gcwt_internal_set_error(code, m.c_str()); }
 
 // Circular convolution engine of one power-of-two length P = P1 * 4096 (<= 2^22): owns the
 // stream, the twiddle tables and three P-point work arrays.
@@ -100,18 +96,6 @@ int check_device(int device) {
   if (device >= 0 && hipSetDevice(device) != hipSuccess)
     return fail(GCWT_ERR_HIP, "hipSetDevice failed");
   return GCWT_OK;
-}
-
-// nothing may unwind across the C ABI
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(GCWT_ERR_NOMEM, "out of host memory");
-  } catch (...) {
-    return fail(GCWT_ERR_INVALID, "internal error");
-  }
 }
 
 int engine_error(const ChirpEngine& e) {

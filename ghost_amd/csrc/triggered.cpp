@@ -4,34 +4,21 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 #include <string>
 
-#include "../../include/ghostcwt.h"
 #include "../../include/ghostcwt_debug.h"
+#include "errors.h"
+#include "resident_op.h"
 #include "triggered.h"
-
-int gcwt_internal_set_error(int code, const char* msg);   // api.cpp (C++ linkage)
 
 static_assert(gcwt::kTrgRows == GCWT_TRIGGERED_TILE_ROWS && gcwt::kTrgLags == GCWT_TRIGGERED_TILE_LAGS,
               "ghostcwt_debug.h names the tile the kernel is built for");
 
+using namespace gcwt;
+
 namespace {
 
-int fail(int code, const std::string& m) { return gcwt_internal_set_error(code, m.c_str()); }
-
-// nothing may unwind across the C ABI
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(GCWT_ERR_NOMEM, "out of host memory");
-  } catch (...) {
-    return fail(GCWT_ERR_INVALID, "internal error");
-  }
-}
-
+constexpr const char* kOp = "gcwt_triggered";
 constexpr int64_t kMaxEvents = int64_t(1) << 24;            // (float)E is exact
 
 // the grid of (n_channels, n_rows, before, after), each already checked
@@ -51,11 +38,10 @@ int cut(int32_t n_channels, int32_t n_rows, int64_t before, int64_t after, gcwt:
 // everything that needs no device; fills the grid's numbers
 int check_and_cut(const int64_t* events, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   int32_t row_first, int32_t n_rows, int64_t n_events, int64_t before, int64_t after, gcwt::TrgArgs* a) {
-  if (n_channels < 1) return fail(GCWT_ERR_INVALID, "gcwt_triggered: n_channels must be at least 1");
-  if (n_scales < 1 || n_cols < 1 || pitch < n_cols)
-    return fail(GCWT_ERR_INVALID, "gcwt_triggered: bad rows (n_scales, n_cols >= 1, pitch >= n_cols)");
-  if (row_first < 0 || n_rows < 1 || n_rows > n_scales - row_first)
-    return fail(GCWT_ERR_INVALID, "gcwt_triggered: the rows must be a non-empty range inside [0, n_scales)");
+  int rc = check_channels(kOp, n_channels);
+  if (!rc) rc = check_rows(kOp, n_scales, n_cols, pitch);
+  if (!rc) rc = check_row_range(kOp, "rows", row_first, n_rows, n_scales);
+  if (rc) return rc;
   if (n_events < 1 || n_events > kMaxEvents)
     return fail(GCWT_ERR_INVALID, "gcwt_triggered: n_events must be in 1 .. 2^24");
   if (before < 0 || after < 0)
@@ -97,52 +83,30 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
     if (!d_rows) return fail(GCWT_ERR_INVALID, "gcwt_triggered: d_rows is NULL");
     if (!events) return fail(GCWT_ERR_INVALID, "gcwt_triggered: events is NULL");
     gcwt::TrgArgs a{};
-    const int rc = check_and_cut(events, pitch, n_channels, n_scales, n_cols, row_first, n_rows, n_events, before, after, &a);
+    int rc = check_and_cut(events, pitch, n_channels, n_scales, n_cols, row_first, n_rows, n_events, before, after, &a);
     if (rc) return rc;
     if (!d_amplitude && !d_power && !d_evoked && !d_vector && !d_itpc)
       return fail(GCWT_ERR_INVALID, "gcwt_triggered: nothing to compute (no output)");
     if (out_pitch < a.n_lags) return fail(GCWT_ERR_INVALID, "gcwt_triggered: out_pitch is below the number of lags, before + after + 1");
 
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_NO_DEVICE, "no HIP device: libghostcwt has no CPU path");
-    }
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_rows) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-      (void)hipGetLastError();
-      return fail(GCWT_ERR_INVALID, "gcwt_triggered: d_rows is not device memory");
-    }
-    const int device = attr.device;
-    for (const void* out : {(const void*)d_amplitude, (const void*)d_power, (const void*)d_evoked, (const void*)d_vector,
-                            (const void*)d_itpc}) {
-      if (!out) continue;
-      if (hipPointerGetAttributes(&attr, out) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) {
-        (void)hipGetLastError();
-        return fail(GCWT_ERR_INVALID, "gcwt_triggered: an output is not memory of the device that holds d_rows");
-      }
-    }
-    hipError_t e = hipSetDevice(device);                   // (the calling thread's device, from here on)
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = resolve_device(kOp, d_rows, {d_amplitude, d_power, d_evoked, d_vector, d_itpc});
+    if (rc) return rc;
 
-    void* d_events = nullptr;
+    DeviceCopy ev;
     const size_t bytes = (size_t)n_events * sizeof(int64_t);
-    e = hipMalloc(&d_events, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
+    hipError_t e = ev.alloc(bytes);
+    if (e != hipSuccess)
       return fail(GCWT_ERR_NOMEM, std::string("gcwt_triggered: no device memory for the event list: ") + hipGetErrorString(e));
-    }
-    e = hipMemcpy(d_events, events, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      a.rows = reinterpret_cast<const float2*>(d_rows);
-      a.events = static_cast<const int64_t*>(d_events);
-      a.out_pitch = out_pitch;
-      a.amplitude = d_amplitude; a.power = d_power; a.itpc = d_itpc;
-      a.evoked = reinterpret_cast<float2*>(d_evoked); a.vector = reinterpret_cast<float2*>(d_vector);
-      e = gcwt::launch_triggered(a, nullptr);
-      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    }
-    (void)hipFree(d_events);
+    e = ev.put(0, events, bytes);
+    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_triggered: ") + hipGetErrorString(e));
+
+    a.rows = reinterpret_cast<const float2*>(d_rows);
+    a.events = static_cast<const int64_t*>(ev.p);
+    a.out_pitch = out_pitch;
+    a.amplitude = d_amplitude; a.power = d_power; a.itpc = d_itpc;
+    a.evoked = reinterpret_cast<float2*>(d_evoked); a.vector = reinterpret_cast<float2*>(d_vector);
+    e = gcwt::launch_triggered(a, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_triggered: ") + hipGetErrorString(e));
     return (int)GCWT_OK;
   });

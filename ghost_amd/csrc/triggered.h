@@ -7,12 +7,13 @@
 
 #include <cstdint>
 
+#include "resident_op.h"
+
 namespace gcwt {
 
 constexpr int kTrgRows = 4;                       // rows per tile: one per wave when the chains are combined
 constexpr int kTrgLags = 64;                      // lags per tile: lane = lag
 constexpr int kTrgChains = 4;                     // interleaved chains of a sum: chain j adds events j, j + 4, ...
-constexpr int kTrgShare = 8;                      // workgroups b and b + kTrgShare share an L2 (triggered.hip: the grid)
 
 struct TrgArgs {
   const float2* rows;          // [channel][scale] rows, pitch complex elements apart
@@ -25,10 +26,8 @@ struct TrgArgs {
   float2* vector;              // [C][n_rows][out_pitch] or NULL
   float* itpc;                 // [C][n_rows][out_pitch] or NULL
 };
-// workgroups of the grid: every (unit, row tile), units padded to a multiple of kTrgShare
-inline int64_t triggered_blocks(const TrgArgs& a) {
-  return (a.n_units + kTrgShare - 1) / kTrgShare * kTrgShare * a.n_rtiles;
-}
+// workgroups of the grid: the row tiles of a unit share its columns (resident_op.h: the placement)
+inline int64_t triggered_blocks(const TrgArgs& a) { return shared_blocks(a.n_units, a.n_rtiles); }
 hipError_t launch_triggered(const TrgArgs& a, hipStream_t st);
 
 }  // namespace gcwt

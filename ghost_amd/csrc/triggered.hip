@@ -23,14 +23,14 @@
 // four waves meet through LDS; wave i then combines the chains of row i, divides and stores.  A tile whose rows and
 // lags all exist takes an instantiation without tests in the event loop.
 //
-// The grid: workgroups b and b + 8 are dealt to the same XCD, so the row tiles of one (channel, lag tile) -- which read
-// the same columns of neighbouring rows and the same events -- are placed 8 apart: index = (group of 8 units, row tile,
-// unit in the group).  This is for speed only; nothing depends on the placement.
+// The grid: the row tiles of one (channel, lag tile) read the same columns of neighbouring rows and the same events, and
+// are placed to meet them in one L2 (resident_op.h: the placement).  This is for speed only; nothing depends on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "triggered.h"
+#include "wave_reduce.h"
 
 namespace gcwt {
 
@@ -42,7 +42,7 @@ struct Acc { float a, p, er, ei, vx, vy; };
 
 // one term enters its chain: the prescribed sequence
 __device__ __forceinline__ void add_term(Acc& s, float2 w) {
-  const float r2 = fmaf(w.y, w.y, __fmul_rn(w.x, w.x));
+  const float r2 = norm2(w);
   const float r = __builtin_sqrtf(r2);
   const float inv = r > 0.f ? 1.0f / r : 0.f;
   s.a = __fadd_rn(s.a, r);
@@ -123,19 +123,15 @@ __device__ __forceinline__ void run_tile(const TrgArgs& a, int ch, int rt, int64
   if (a.power) a.power[o] = x[1] / cnt;
   if (a.evoked) a.evoked[o] = make_float2(x[2] / cnt, x[3] / cnt);
   if (a.vector) a.vector[o] = make_float2(x[4] / cnt, x[5] / cnt);
-  if (a.itpc) a.itpc[o] = fminf(__builtin_sqrtf(fmaf(x[5], x[5], __fmul_rn(x[4], x[4]))) / cnt, 1.f);
+  if (a.itpc) a.itpc[o] = fminf(modulus(make_float2(x[4], x[5])) / cnt, 1.f);
 }
 
 __global__ void __launch_bounds__(64 * kTrgChains) k_triggered(TrgArgs a) {
   __shared__ float s_red[kTrgChains][kTrgRows][kSums][kTrgLags];
-  int64_t idx = blockIdx.x;                                  // (group of kTrgShare units, row tile, unit in the group)
-  const int member = (int)(idx % kTrgShare);
-  idx /= kTrgShare;
-  const int rt = (int)(idx % a.n_rtiles);
-  const int64_t unit = idx / a.n_rtiles * kTrgShare + member;
-  if (unit >= a.n_units) return;                             // (the last group's padding)
-  const int ch = (int)(unit / a.n_ltiles);
-  const int64_t lt = unit % a.n_ltiles;
+  const TileOfUnit at = shared_place(a.n_rtiles);            // unit = (channel, lag tile)
+  if (at.unit >= a.n_units) return;                          // (the last group's padding)
+  const int rt = at.tile, ch = (int)(at.unit / a.n_ltiles);
+  const int64_t lt = at.unit % a.n_ltiles;
   if ((rt + 1) * kTrgRows <= a.n_rows && (lt + 1) * kTrgLags <= a.n_lags)
     run_tile<true>(a, ch, rt, lt, s_red);
   else

@@ -182,7 +182,7 @@ def coherence_pairs(pairs, seed, n_channels):
     return np.ascontiguousarray(arr, dtype=np.int32)
 
 
-def coherence_window(window):
+def bin_window(window):
     """The bin width as an int: an integer >= 2 (numpy integers too); anything else raises ValueError."""
     if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
         raise ValueError("window must be an integer >= 2 (columns per bin), not %r" % (window,))
@@ -191,7 +191,78 @@ def coherence_window(window):
     return int(window)
 
 
-class CoherenceResult:
+coherence_window = bin_window                               # (the name it had while coherence() was its only user)
+
+
+class _RowOpResult:
+    """What an operator on the rows of a resident result left on the device: planes of float32 / complex64 rows, ``pitch``
+    elements apart, one after the other in one DeviceBuffer.  A subclass's ``_planes()`` says which: ((name, dtype,
+    leading shape), ...) in buffer order, and how many elements of a row are live."""
+
+    def _plane_bytes(self):
+        return [(name, int(np.prod(lead, dtype=np.int64)) * self.pitch * np.dtype(dtype).itemsize)
+                for name, dtype, lead in self._planes()[0]]
+
+    def _offsets(self):
+        """name -> the plane's first byte."""
+        offsets, end = {}, 0
+        for name, nbytes in self._plane_bytes():
+            offsets[name] = end
+            end += nbytes
+        return offsets
+
+    @property
+    def nbytes(self):
+        return sum(nbytes for _, nbytes in self._plane_bytes())
+
+    def to_host(self):
+        """name -> dense ndarray, for every plane."""
+        planes, live = self._planes()
+        offsets = self._offsets()
+        return {name: np.ascontiguousarray(self.buffer.download(tuple(lead) + (self.pitch,), dtype, offsets[name])[..., :live])
+                for name, dtype, lead in planes}
+
+    def free(self):
+        if self.buffer is not None:
+            self.buffer.free()
+            self.buffer = None
+
+
+def _pitch(n):
+    return (n + 31) & ~31                                   # rows start on 128-byte lines
+
+
+def _resident_complex(result, what, sharded_reason):
+    """The shape (C, S, N) of ``result`` if operator ``what`` can work on it: a complex DeviceResult that still has its
+    buffer."""
+    if not isinstance(result, DeviceResult):
+        raise ValueError("%s() takes a DeviceResult on one device (%s)" % (what, sharded_reason))
+    if result.buffer is None:
+        raise ValueError("the result has been freed")
+    if not result.is_complex:
+        raise ValueError("%s() needs complex coefficients (output='complex')" % what)
+    return result.shape
+
+
+def _run_into(res, what, sizes, advice, call):
+    """Gives ``res`` its buffer -- MemoryError, in the operator's words, where the device has not that much free -- and
+    runs ``call(ptr)``, ptr: plane name -> c_void_p; a call that fails takes the buffer with it.  -> res."""
+    nbytes = res.nbytes
+    free, _ = device_memory()
+    if nbytes > free:
+        raise MemoryError("%s() needs %d bytes on the device for its outputs (%s) and %d are free: %s"
+                          % (what, nbytes, sizes, free, advice))
+    res.buffer = buf = DeviceBuffer(nbytes)
+    ptr = {name: C.c_void_p(buf.ptr.value + off) for name, off in res._offsets().items()}
+    try:
+        call(ptr)
+    except Exception:
+        res.free()
+        raise
+    return res
+
+
+class CoherenceResult(_RowOpResult):
     """What coherence() left on the device: ``coherence`` (P, S, B) float32, ``cross`` (P, S, B) complex64 and ``power``
     (C, S, B) float32 in one DeviceBuffer, rows ``pitch`` elements apart; ``pairs`` (P, 2); ``window``; ``counts`` (B,):
     the columns of each bin.  ``to_host()`` brings the three over."""
@@ -200,67 +271,30 @@ class CoherenceResult:
         self.buffer, self.pairs, self.pitch, self.window, self.counts = buffer, pairs, int(pitch), int(window), counts
         self.n_pairs, self.n_channels, self.n_scales, self.n_bins = len(pairs), int(n_channels), int(n_scales), int(n_bins)
 
-    # the buffer holds cross, then coherence, then power
-    def _offsets(self):
-        rows = self.n_pairs * self.n_scales * self.pitch
-        return 0, rows * 8, rows * 12
+    def _planes(self):
+        p, c, s = self.n_pairs, self.n_channels, self.n_scales
+        return (("cross", np.complex64, (p, s)), ("coherence", np.float32, (p, s)), ("power", np.float32, (c, s))), self.n_bins
 
-    @property
-    def nbytes(self):
-        return (3 * self.n_pairs + self.n_channels) * self.n_scales * self.pitch * 4
 
-    def to_host(self):
-        """{"coherence", "cross", "power"}: dense ndarrays."""
-        p, c, s, b = self.n_pairs, self.n_channels, self.n_scales, self.n_bins
-        o_cross, o_coh, o_pow = self._offsets()
-        cross = self.buffer.download((p, s, self.pitch), np.complex64, o_cross)[..., :b]
-        coh = self.buffer.download((p, s, self.pitch), np.float32, o_coh)[..., :b]
-        power = self.buffer.download((c, s, self.pitch), np.float32, o_pow)[..., :b]
-        return {"coherence": np.ascontiguousarray(coh), "cross": np.ascontiguousarray(cross),
-                "power": np.ascontiguousarray(power)}
-
-    def free(self):
-        if self.buffer is not None:
-            self.buffer.free()
-            self.buffer = None
+def _bin_counts(n, window, n_bins):
+    return np.minimum(window, n - np.arange(n_bins, dtype=np.int64) * window)
 
 
 def coherence(result, pairs, window):
     """Binned cross-spectra of channel pairs of a complex DeviceResult, computed where it lies (gcwt_coherence: bins of
     ``window`` columns; include/ghostcwt.h has the definition).  ``pairs``: (P, 2) as coherence_pairs returns them.  The
     result itself is only read.  -> CoherenceResult."""
-    window = coherence_window(window)
-    if not isinstance(result, DeviceResult):
-        raise ValueError("coherence() takes a DeviceResult on one device (the channels of a result sharded over "
-                         "several GPUs cannot be paired)")
-    if result.buffer is None:
-        raise ValueError("the result has been freed")
-    if not result.is_complex:
-        raise ValueError("coherence() needs complex coefficients (output='complex')")
-    c, s, n = result.shape
+    window = bin_window(window)
+    c, s, n = _resident_complex(result, "coherence", "the channels of a result sharded over several GPUs cannot be paired")
     pairs = coherence_pairs(pairs, None, c)
     n_bins = -(-n // window)
-    pitch = (n_bins + 31) & ~31
     p = len(pairs)
-    nbytes = (3 * p + c) * s * pitch * 4
-    free, _ = device_memory()
-    if nbytes > free:
-        raise MemoryError("coherence() needs %d bytes on the device for its outputs (%d pairs, %d channels, %d "
-                          "scales, %d bins) and %d are free: fewer pairs or a wider window"
-                          % (nbytes, p, c, s, n_bins, free))
-    buf = DeviceBuffer(nbytes)
-    res = CoherenceResult(buf, pairs, c, s, n_bins, pitch, window,
-                          np.minimum(window, n - np.arange(n_bins, dtype=np.int64) * window))
-    o_cross, o_coh, o_pow = res._offsets()
-    base = buf.ptr.value
-    try:
-        check(lib.gcwt_coherence(result.buffer.ptr, result.pitch, c, s, n, pairs.ctypes.data_as(C.POINTER(C.c_int32)), p,
-                                 window, C.c_void_p(base + o_pow), C.c_void_p(base + o_cross), C.c_void_p(base + o_coh),
-                                 pitch))
-    except Exception:
-        res.free()
-        raise
-    return res
+    res = CoherenceResult(None, pairs, c, s, n_bins, _pitch(n_bins), window, _bin_counts(n, window, n_bins))
+    return _run_into(
+        res, "coherence", "%d pairs, %d channels, %d scales, %d bins" % (p, c, s, n_bins), "fewer pairs or a wider window",
+        lambda ptr: check(lib.gcwt_coherence(result.buffer.ptr, result.pitch, c, s, n,
+                                             pairs.ctypes.data_as(C.POINTER(C.c_int32)), p, window, ptr["power"],
+                                             ptr["cross"], ptr["coherence"], res.pitch)))
 
 
 def coupling_rows(limits, frequencies, what):
@@ -288,7 +322,7 @@ def coupling_rows(limits, frequencies, what):
     return int(rows[0]), int(rows.size)
 
 
-class CouplingResult:
+class CouplingResult(_RowOpResult):
     """What coupling() left on the device: ``vector`` (C, P, A, B) complex64, ``mvl`` (C, P, A, B) float32 and
     ``amplitude`` (C, A, B) float32 in one DeviceBuffer, rows ``pitch`` elements apart; ``phase_rows`` and ``amp_rows``:
     (first, count); ``window``; ``counts`` (B,): the columns of each bin.  ``to_host()`` brings the three over."""
@@ -298,29 +332,9 @@ class CouplingResult:
         self.phase_rows, self.amp_rows = tuple(phase_rows), tuple(amp_rows)
         self.n_channels, self.n_phase, self.n_amp, self.n_bins = int(n_channels), int(phase_rows[1]), int(amp_rows[1]), int(n_bins)
 
-    # the buffer holds vector, then mvl, then amplitude
-    def _offsets(self):
-        rows = self.n_channels * self.n_phase * self.n_amp * self.pitch
-        return 0, rows * 8, rows * 12
-
-    @property
-    def nbytes(self):
-        return (3 * self.n_phase + 1) * self.n_channels * self.n_amp * self.pitch * 4
-
-    def to_host(self):
-        """{"vector", "mvl", "amplitude"}: dense ndarrays."""
-        c, p, a, b = self.n_channels, self.n_phase, self.n_amp, self.n_bins
-        o_vec, o_mvl, o_amp = self._offsets()
-        vec = self.buffer.download((c, p, a, self.pitch), np.complex64, o_vec)[..., :b]
-        mvl = self.buffer.download((c, p, a, self.pitch), np.float32, o_mvl)[..., :b]
-        amp = self.buffer.download((c, a, self.pitch), np.float32, o_amp)[..., :b]
-        return {"vector": np.ascontiguousarray(vec), "mvl": np.ascontiguousarray(mvl),
-                "amplitude": np.ascontiguousarray(amp)}
-
-    def free(self):
-        if self.buffer is not None:
-            self.buffer.free()
-            self.buffer = None
+    def _planes(self):
+        c, p, a = self.n_channels, self.n_phase, self.n_amp
+        return (("vector", np.complex64, (c, p, a)), ("mvl", np.float32, (c, p, a)), ("amplitude", np.float32, (c, a))), self.n_bins
 
 
 def _row_range(rows, n_scales, what):
@@ -338,38 +352,18 @@ def coupling(result, phase_rows, amp_rows, window):
     """Binned phase-amplitude coupling inside every channel of a complex DeviceResult, computed where it lies
     (gcwt_coupling: bins of ``window`` columns; include/ghostcwt.h has the definition).  ``phase_rows``, ``amp_rows``:
     (first, count) as coupling_rows returns them; they may overlap.  The result itself is only read.  -> CouplingResult."""
-    window = coherence_window(window)
-    if not isinstance(result, DeviceResult):
-        raise ValueError("coupling() takes a DeviceResult on one device (a result sharded over several GPUs is not "
-                         "supported)")
-    if result.buffer is None:
-        raise ValueError("the result has been freed")
-    if not result.is_complex:
-        raise ValueError("coupling() needs complex coefficients (output='complex')")
-    c, s, n = result.shape
+    window = bin_window(window)
+    c, s, n = _resident_complex(result, "coupling", "a result sharded over several GPUs is not supported")
     phase_rows = _row_range(phase_rows, s, "phase_rows")
     amp_rows = _row_range(amp_rows, s, "amp_rows")
     n_bins = -(-n // window)
-    pitch = (n_bins + 31) & ~31
-    res = CouplingResult(None, c, phase_rows, amp_rows, n_bins, pitch, window,
-                         np.minimum(window, n - np.arange(n_bins, dtype=np.int64) * window))
-    nbytes = res.nbytes
-    free, _ = device_memory()
-    if nbytes > free:
-        raise MemoryError("coupling() needs %d bytes on the device for its outputs (%d channels, %d x %d rows, %d bins) "
-                          "and %d are free: narrower bands or a wider window"
-                          % (nbytes, c, phase_rows[1], amp_rows[1], n_bins, free))
-    res.buffer = buf = DeviceBuffer(nbytes)
-    o_vec, o_mvl, o_amp = res._offsets()
-    base = buf.ptr.value
-    try:
-        check(lib.gcwt_coupling(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1], amp_rows[0],
-                                amp_rows[1], window, C.c_void_p(base + o_vec), C.c_void_p(base + o_mvl),
-                                C.c_void_p(base + o_amp), pitch))
-    except Exception:
-        res.free()
-        raise
-    return res
+    res = CouplingResult(None, c, phase_rows, amp_rows, n_bins, _pitch(n_bins), window, _bin_counts(n, window, n_bins))
+    return _run_into(
+        res, "coupling", "%d channels, %d x %d rows, %d bins" % (c, phase_rows[1], amp_rows[1], n_bins),
+        "narrower bands or a wider window",
+        lambda ptr: check(lib.gcwt_coupling(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1],
+                                            amp_rows[0], amp_rows[1], window, ptr["vector"], ptr["mvl"], ptr["amplitude"],
+                                            res.pitch)))
 
 
 def _seconds(value, what):
@@ -434,7 +428,7 @@ def trigger_columns(events, time, fs, stride, before, after, n_cols=None):
     return _trigger_scan(events, time, fs, stride, before, after, n_cols)[:4]
 
 
-class TriggeredResult:
+class TriggeredResult(_RowOpResult):
     """What triggered() left on the device, each (C, R, L) with rows ``pitch`` elements apart in one DeviceBuffer:
     ``evoked`` and ``vector`` complex64, ``amplitude``, ``power`` and ``itpc`` float32; ``rows``: (first, count);
     ``n_before``, ``n_after`` columns, L = n_before + n_after + 1 lags; ``n_events``.  ``to_host()`` brings the five over."""
@@ -444,26 +438,10 @@ class TriggeredResult:
         self.n_channels, self.n_rows, self.n_events = int(n_channels), int(rows[1]), int(n_events)
         self.n_before, self.n_after, self.n_lags = int(n_before), int(n_after), int(n_before) + int(n_after) + 1
 
-    # the buffer holds evoked, vector, then amplitude, power, itpc
-    def _offsets(self):
-        plane = self.n_channels * self.n_rows * self.pitch * 4
-        return {"evoked": 0, "vector": 2 * plane, "amplitude": 4 * plane, "power": 5 * plane, "itpc": 6 * plane}
-
-    @property
-    def nbytes(self):
-        return 7 * self.n_channels * self.n_rows * self.pitch * 4
-
-    def to_host(self):
-        """{"amplitude", "power", "evoked", "vector", "itpc"}: dense ndarrays."""
-        shape = (self.n_channels, self.n_rows, self.pitch)
-        return {name: np.ascontiguousarray(self.buffer.download(shape, np.complex64 if name in ("evoked", "vector")
-                                                                else np.float32, off)[..., :self.n_lags])
-                for name, off in self._offsets().items()}
-
-    def free(self):
-        if self.buffer is not None:
-            self.buffer.free()
-            self.buffer = None
+    def _planes(self):
+        lead = (self.n_channels, self.n_rows)
+        return (("evoked", np.complex64, lead), ("vector", np.complex64, lead), ("amplitude", np.float32, lead),
+                ("power", np.float32, lead), ("itpc", np.float32, lead)), self.n_lags
 
 
 def _columns(value, what):
@@ -478,14 +456,7 @@ def triggered(result, cols, nb, na, rows=None):
     is part of the definition of the float32 sums) the window of ``nb`` columns before and ``na`` after, which must lie
     inside the result for every event -- trigger_columns() makes such a list from event times.  ``rows``: (first, count),
     default all rows.  The result itself is only read.  -> TriggeredResult."""
-    if not isinstance(result, DeviceResult):
-        raise ValueError("triggered() takes a DeviceResult on one device (a result sharded over several GPUs is not "
-                         "supported)")
-    if result.buffer is None:
-        raise ValueError("the result has been freed")
-    if not result.is_complex:
-        raise ValueError("triggered() needs complex coefficients (output='complex')")
-    c, s, n = result.shape
+    c, s, n = _resident_complex(result, "triggered", "a result sharded over several GPUs is not supported")
     nb, na = _columns(nb, "nb"), _columns(na, "na")
     rows = _row_range((0, s) if rows is None else rows, s, "rows")
     arr = np.asarray(cols)
@@ -501,24 +472,12 @@ def triggered(result, cols, nb, na, rows=None):
     if bad.size:
         raise ValueError("cols[%d] = %d: its window of %d columns before and %d after leaves the result's %d columns"
                          % (bad[0], arr[bad[0]], nb, na, n))
-    pitch = (n_lags + 31) & ~31
-    res = TriggeredResult(None, c, rows, nb, na, pitch, arr.size)
-    nbytes = res.nbytes
-    free, _ = device_memory()
-    if nbytes > free:
-        raise MemoryError("triggered() needs %d bytes on the device for its outputs (%d channels, %d rows, %d lags) "
-                          "and %d are free: fewer rows or a shorter window"
-                          % (nbytes, c, rows[1], n_lags, free))
-    res.buffer = buf = DeviceBuffer(nbytes)
-    ptr = {name: C.c_void_p(buf.ptr.value + off) for name, off in res._offsets().items()}
-    try:
-        check(lib.gcwt_triggered(result.buffer.ptr, result.pitch, c, s, n, rows[0], rows[1],
-                                 arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, nb, na, ptr["amplitude"], ptr["power"],
-                                 ptr["evoked"], ptr["vector"], ptr["itpc"], pitch))
-    except Exception:
-        res.free()
-        raise
-    return res
+    res = TriggeredResult(None, c, rows, nb, na, _pitch(n_lags), arr.size)
+    return _run_into(
+        res, "triggered", "%d channels, %d rows, %d lags" % (c, rows[1], n_lags), "fewer rows or a shorter window",
+        lambda ptr: check(lib.gcwt_triggered(result.buffer.ptr, result.pitch, c, s, n, rows[0], rows[1],
+                                             arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, nb, na, ptr["amplitude"],
+                                             ptr["power"], ptr["evoked"], ptr["vector"], ptr["itpc"], res.pitch)))
 
 
 def stride_columns(start, stop, stride):

@@ -339,6 +339,21 @@ class ContinuousWaveletTransform(WaveletTransform):
             res = self._device_result.to_host(np.float64 if wide else np.float32, scales, start, stop)
         return res[0] if squeeze else res
 
+    def _resident_rows(self, what, one_device="works", sharded="which is not supported"):
+        """(the last transform's DeviceResult, squeeze) for operator ``what``; ValueError where there is none, it is not
+        complex, or it is sharded over several devices."""
+        from .. import engine
+        if self._device_result is None or (self._pending is None and self._last_kind is None):
+            raise ValueError("no transform on the device (call transform() first)")
+        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
+        if out_kind != "complex":
+            raise ValueError("%s() needs the complex coefficients: the last transform was output='%s', "
+                             "not output='complex'" % (what, out_kind))
+        if not isinstance(self._device_result, engine.DeviceResult):
+            raise ValueError("%s() %s on one device: the last transform was sharded over several "
+                             "(devices=[...]), %s" % (what, one_device, sharded))
+        return self._device_result, squeeze
+
     def coherence(self, pairs=None, *, seed=None, window):
         """Wavelet coherence and cross-spectra between channels of the last transform, reduced on the device over bins
         of ``window`` columns (an integer >= 2; with an output stride K a column is K samples) -- the transform must
@@ -354,21 +369,13 @@ class ContinuousWaveletTransform(WaveletTransform):
         periods of the lowest frequency of interest.  Only the reduced arrays cross to the host; the resident result,
         ``fetch()`` and the result attributes are untouched."""
         from .. import engine
-        window = engine.coherence_window(window)
-        if self._device_result is None or (self._pending is None and self._last_kind is None):
-            raise ValueError("no transform on the device (call transform() first)")
-        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
-        if out_kind != "complex":
-            raise ValueError("coherence() needs the complex coefficients: the last transform was output='%s', "
-                             "not output='complex'" % out_kind)
-        if not isinstance(self._device_result, engine.DeviceResult):
-            raise ValueError("coherence() pairs channels on one device: the last transform was sharded over several "
-                             "(devices=[...]), and pairs across devices are not supported")
-        if squeeze or self._device_result.shape[0] < 2:
+        window = engine.bin_window(window)
+        result, squeeze = self._resident_rows("coherence", "pairs channels", "and pairs across devices are not supported")
+        if squeeze or result.shape[0] < 2:
             raise ValueError("coherence() relates channels: the last transform must be multichannel=True with at "
                              "least 2 channels")
-        pairs = engine.coherence_pairs(pairs, seed, self._device_result.shape[0])
-        res = engine.coherence(self._device_result, pairs, window)
+        pairs = engine.coherence_pairs(pairs, seed, result.shape[0])
+        res = engine.coherence(result, pairs, window)
         try:
             out = res.to_host()
         finally:
@@ -395,20 +402,12 @@ class ContinuousWaveletTransform(WaveletTransform):
         Only the reduced arrays cross to the host; the resident result, ``fetch()`` and the result attributes are
         untouched."""
         from .. import engine
-        window = engine.coherence_window(window)
-        if self._device_result is None or (self._pending is None and self._last_kind is None):
-            raise ValueError("no transform on the device (call transform() first)")
-        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
-        if out_kind != "complex":
-            raise ValueError("coupling() needs the complex coefficients: the last transform was output='%s', "
-                             "not output='complex'" % out_kind)
-        if not isinstance(self._device_result, engine.DeviceResult):
-            raise ValueError("coupling() works on one device: the last transform was sharded over several "
-                             "(devices=[...]), which is not supported")
+        window = engine.bin_window(window)
+        result, squeeze = self._resident_rows("coupling")
         f = np.array(self._frequencies)
         phase_rows = engine.coupling_rows(phase, f, "phase")
         amp_rows = engine.coupling_rows(amplitude, f, "amplitude")
-        res = engine.coupling(self._device_result, phase_rows, amp_rows, window)
+        res = engine.coupling(result, phase_rows, amp_rows, window)
         try:
             out = res.to_host()
         finally:
@@ -440,26 +439,17 @@ class ContinuousWaveletTransform(WaveletTransform):
         Only the reduced arrays cross to the host; the resident result, ``fetch()`` and the result attributes are
         untouched."""
         from .. import engine
-        if self._device_result is None or (self._pending is None and self._last_kind is None):
-            raise ValueError("no transform on the device (call transform() first)")
-        out_kind, _, squeeze = self._pending if self._pending is not None else self._last_kind
-        if out_kind != "complex":
-            raise ValueError("triggered() needs the complex coefficients: the last transform was output='%s', "
-                             "not output='complex'" % out_kind)
-        if not isinstance(self._device_result, engine.DeviceResult):
-            raise ValueError("triggered() works on one device: the last transform was sharded over several "
-                             "(devices=[...]), which is not supported")
+        result, squeeze = self._resident_rows("triggered")
         f = np.array(self._frequencies)
         rows = (0, f.size) if freq_limits is None else engine.coupling_rows(freq_limits, f, "freq_limits")
         stride, fs = self._stride, float(self._fs)
-        cols, used, nb, na, why = engine._trigger_scan(events, self.time, fs, stride, before, after,
-                                                       self._device_result.shape[2])
+        cols, used, nb, na, why = engine._trigger_scan(events, self.time, fs, stride, before, after, result.shape[2])
         if cols.size == 0:
             raise ValueError("triggered(): none of the %d events can be used: %d lie in a gap between epochs or outside "
                              "the recording, %d have a window (%d columns before, %d after) that leaves the recording, "
                              "%d have a window that would splice two epochs"
                              % (used.size, why["gap"], why["edge"], nb, na, why["splice"]))
-        res = engine.triggered(self._device_result, cols, nb, na, rows)
+        res = engine.triggered(result, cols, nb, na, rows)
         try:
             out = res.to_host()
         finally:
