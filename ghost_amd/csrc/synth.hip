@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) v[k1] = exr[k1 * kPlane];
     if (!(kMeasureBuild && (a.drop_stores & 2))) __syncthreads();
-    idft16v(v);
+    idft16v<true>(v);                          // strict: |.| rows round as k_synth7s's do, and as the complex rows
 
     // descriptor built from provably wave-uniform words (else hipcc waterfalls every store)
     const int srow = entry & kScaleIndexMask;

@@ -100,20 +100,31 @@ __device__ __forceinline__ void gain_first_layer_c(v2f v[16], const v2f p[16], c
   bfly4_in<(11 >= JHI), (15 >= JHI)>(v[3], v[7], v[11], v[15]);
 }
 
-// the rest of idft16v after its first layer: twiddles W16^(n1 k2), second radix-4 layer
+// a * (s, s) as the packed multiply itself: the compiler cannot contract it into the adds that follow
+__device__ __forceinline__ v2f scalev(v2f a, v2f s) {
+  v2f r;
+  asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(s));
+  return r;
+}
+
+// the rest of idft16v after its first layer: twiddles W16^(n1 k2), second radix-4 layer.  STRICT: the two real
+// twiddles are multiplied as written, never fused with the butterfly's adds -- which the compiler otherwise does in
+// some instantiations of a kernel and not in others (k_synth7's |.| modes, but not k_synth7s's: synths.hip)
+template <bool STRICT = false>
 __device__ __forceinline__ void idft16v_tail(v2f v[16]) {
   const v2f w1 = {0.92387953251128674f, 0.38268343236508977f};   // W16^1
   const v2f w3 = {0.38268343236508977f, 0.92387953251128674f};   // W16^3
   const v2f w9 = {-0.92387953251128674f, -0.38268343236508977f}; // W16^9
   const float h = 0.70710678118654752f;
   // v[n1 + 4 k2] *= W16^(n1 k2); W16^2 = h(1+i), W16^6 = h(-1+i); W16^4 = i is folded below
+  const auto times = [](v2f a, float s) { if constexpr (STRICT) return scalev(a, (v2f){s, s}); else return a * s; };
   v[5] = cmulv(v[5], w1);
-  v[9] = add_ib(v[9], v[9]) * h;
+  v[9] = times(add_ib(v[9], v[9]), h);
   v[13] = cmulv(v[13], w3);
-  v[6] = add_ib(v[6], v[6]) * h;
-  v[14] = sub_ib(v[14], v[14]) * (-h);
+  v[6] = times(add_ib(v[6], v[6]), h);
+  v[14] = times(sub_ib(v[14], v[14]), -h);
   v[7] = cmulv(v[7], w3);
-  v[11] = sub_ib(v[11], v[11]) * (-h);
+  v[11] = times(sub_ib(v[11], v[11]), -h);
   v[15] = cmulv(v[15], w9);
   bfly4<false>(v[0], v[1], v[2], v[3]);
   bfly4<false>(v[4], v[5], v[6], v[7]);
@@ -121,10 +132,11 @@ __device__ __forceinline__ void idft16v_tail(v2f v[16]) {
   bfly4<false>(v[12], v[13], v[14], v[15]);
 }
 
+template <bool STRICT = false>
 __device__ __forceinline__ void idft16v(v2f v[16]) {
 #pragma unroll
   for (int n1 = 0; n1 < 4; ++n1) bfly4<false>(v[n1], v[n1 + 4], v[n1 + 8], v[n1 + 12]);
-  idft16v_tail(v);
+  idft16v_tail<STRICT>(v);
 }
 
 }  // namespace gcwt

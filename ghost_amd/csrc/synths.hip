@@ -343,7 +343,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7s(const
     }
     __syncthreads();
     if (!keep_rows) continue;                  // nothing of this thread's sixteen rows is kept
-    idft16v(v);
+    idft16v<true>(v);                          // strict: the rows are k_synth7's every K-th column bit for bit
 
     // descriptor built from provably wave-uniform words (else hipcc waterfalls every store)
     const int srow = entry & kScaleIndexMask;
