@@ -167,6 +167,37 @@ struct Synth7Args {
   SegOut seg;
 };
 
+// k_synth7's exchange between its two DFT16 passes (synth.hip).  Column colw (threads 16 colw .. 16 colw + 15, phase
+// r = colw mod R of block colw / R) writes elements elem(colw, j), j = 0 .. 15, of the sixteen planes; thread tid
+// reads element tid of every plane.  R <= columns only: above, a column is one phase of the workgroup's one block.
+__host__ __device__ constexpr int synth7_ex_elem(int lg, int colw, int j) {
+  return ((colw >> lg) << (4 + lg)) + (colw & ((1 << lg) - 1)) + (j << lg);
+}
+// The exchange stays inside a wavefront -- every element a wave reads was written by that wave -- when a block's
+// 16 R elements fill at most one wave: the scale loop then needs no workgroup barrier around it, a wave's LDS
+// operations complete in order.  At R = 8 an exchange spans two waves, at R > columns the whole workgroup.
+__host__ __device__ constexpr bool synth7_exchange_wave_local(int ncol, int R) { return R <= ncol && 16 * R <= 64; }
+// the same from the mapping itself: the wave of the writer of every element against the wave of its reader
+constexpr bool synth7_exchange_spans_one_wave(int ncol, int lg) {
+  for (int colw = 0; colw < ncol; ++colw)
+    for (int j = 0; j < 16; ++j)
+      if ((16 * colw) >> 6 != synth7_ex_elem(lg, colw, j) >> 6) return false;
+  return true;
+}
+// What the scale loop tests: the stride between a column's elements in a plane -- R, or the column count at
+// R > columns -- is at most this exactly where the predicate holds (one scalar compare per scale).
+constexpr int kSynth7LocalStride = 4;
+#define GCWT_EX_CHECK(ncol, lg, local)                                                                    \
+  static_assert(synth7_exchange_wave_local(ncol, 1 << (lg)) == (local) &&                                 \
+                    ((1 << (lg)) > (ncol) || synth7_exchange_spans_one_wave(ncol, lg) == (local)) &&      \
+                    (((1 << (lg)) > (ncol) ? (ncol) : (1 << (lg))) <= kSynth7LocalStride) == (local),     \
+                "k_synth7: the wave-local predicate does not match the column mapping")
+GCWT_EX_CHECK(16, 0, true);  GCWT_EX_CHECK(16, 1, true);  GCWT_EX_CHECK(16, 2, true);  GCWT_EX_CHECK(16, 3, false);
+GCWT_EX_CHECK(16, 4, false); GCWT_EX_CHECK(16, 5, false); GCWT_EX_CHECK(16, 6, false);
+GCWT_EX_CHECK(32, 0, true);  GCWT_EX_CHECK(32, 1, true);  GCWT_EX_CHECK(32, 2, true);  GCWT_EX_CHECK(32, 3, false);
+GCWT_EX_CHECK(32, 4, false); GCWT_EX_CHECK(32, 5, false); GCWT_EX_CHECK(32, 6, false); GCWT_EX_CHECK(32, 7, false);
+#undef GCWT_EX_CHECK
+
 // wide_halo: the items' levels have block halos above 48 (k_synth7<.., WIDE>); the other launch takes the rest
 hipError_t launch_synth7(int mode, int ncol, bool wide_halo, const Synth7Args& a, int n_items, int n_channels,
                          hipStream_t st);

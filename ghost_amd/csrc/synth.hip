@@ -29,7 +29,9 @@ namespace gcwt {
 //   v = P * G_s          complex x real, only the inputs below the scale's j_hi (the bins
 //                        above its band are skipped: kernels.h, k_scale_windows), folded
 //                        into the first radix-4 layer
-//   rest of DFT16, W256 twiddle (table in LDS), transpose + re-deal through LDS
+//   rest of DFT16, W256 twiddle (table in LDS), transpose + re-deal through LDS (between two
+//                        workgroup barriers from R = 8 up; at R <= 4 the exchange never leaves a
+//                        wave and the loop has no barrier but the pair around each re-park)
 //   DFT16, |.|, 14 stores of 4 B per lane: 256 contiguous bytes per wave store, nt
 // With 16 <= halo <= 32 rows 0 and 15 of a thread's 16 outputs are always halo,
 // rows 2..13 are always kept and rows 1 / 14 are kept lane-wise.
@@ -256,7 +258,7 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
     if (lv.n_scales > kChunk) load_gains(kChunk);
   }
   const int sstride = wide ? NCOL : R;
-  v2f* const exw = ex + ((t - sh) & 15) * kPlane + (wide ? colw : (blk_l << (4 + lg)) + r);
+  v2f* const exw = ex + ((t - sh) & 15) * kPlane + (wide ? colw : synth7_ex_elem(lg, colw, 0));
   const int blk_l2 = wide ? 0 : (tid >> (4 + lg));
   const int rem = wide ? tid : (tid & ((16 << lg) - 1));
   const int m2 = wide ? (tid >> kLgN) : (rem >> lg);
@@ -332,10 +334,22 @@ __global__ void __launch_bounds__(16 * NCOL, NCOL == 32 ? 4 : 3) k_synth7(const 
       case 32: twiddle_to_planes<32>(exw, v, twl + t * kTwPitch); break;
       default: twiddle_to_planes<0>(exw, v, twl + t * kTwPitch, sstride); break;
     }
-    if (!(kMeasureBuild && (a.drop_stores & 2))) __syncthreads();      // (always taken in the product build: kernels.h)
+    // Element tid of every plane back.  Plane strides up to 4 are the levels whose exchange stays inside a wavefront
+    // (kernels.h: synth7_exchange_wave_local): every element a wave reads it wrote itself, and its LDS operations
+    // complete in order -- no workgroup barrier, only fences at wavefront scope that keep the compiler from moving
+    // the accesses across.  One uniform branch per scale; every other level keeps both barriers.  (The loop compiled
+    // twice, one copy per path, or the reads folded into the switch above, sent the 32-column kernel to scratch memory.)
+    if (__builtin_expect(sstride <= kSynth7LocalStride, 0)) {   // workgroup-uniform; the barrier path falls through
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) v[k1] = exr[k1 * kPlane];
-    if (!(kMeasureBuild && (a.drop_stores & 2))) __syncthreads();
+      for (int k1 = 0; k1 < 16; ++k1) v[k1] = exr[k1 * kPlane];
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    } else {
+      if (!(kMeasureBuild && (a.drop_stores & 2))) __syncthreads();      // (always taken in the product build: kernels.h)
+#pragma unroll
+      for (int k1 = 0; k1 < 16; ++k1) v[k1] = exr[k1 * kPlane];
+      if (!(kMeasureBuild && (a.drop_stores & 2))) __syncthreads();
+    }
     idft16v<true>(v);                          // strict: |.| rows round as k_synth7s's do, and as the complex rows
 
     // descriptor built from provably wave-uniform words (else hipcc waterfalls every store)
