@@ -85,6 +85,8 @@ def _load():
                                     C.c_int64, vp, vp, vp, C.c_int64]),
         "gcwt_triggered": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, i64p, C.c_int64,
                                      C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int64]),
+        "gcwt_bandpass": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, f32p, vp, vp, vp,
+                                    C.c_int64]),
         "gcwt_plan_create": (C.c_int, [C.POINTER(vp), C.POINTER(Params)]),
         "gcwt_plan_destroy": (None, [vp]),
         "gcwt_plan_get_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
@@ -133,6 +135,7 @@ def _load():
         "gcwt_debug_coherence_tasks": (C.c_int, [C.c_int32, i32p, C.c_int32, i32p, i32p, i32p, i32p, i32p, C.c_int32]),
         "gcwt_debug_coupling_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, i32p, i64p, i64p, i64p]),
         "gcwt_debug_triggered_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, i32p, i64p, i64p]),
+        "gcwt_debug_bandpass_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, i64p, i32p, i64p]),
         "gcwt_debug_fetch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int64]),
     }
     for name, (res, args) in sig.items():

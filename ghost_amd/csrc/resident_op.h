@@ -1,5 +1,5 @@
 // resident_op.h -- what the operators that reduce the rows of a resident complex result in place share (coherence,
-// coupling, triggered): the host's argument checks, the device that holds the rows, a temporary device copy of a host
+// coupling, triggered, bandpass): the host's argument checks, the device that holds the rows, a temporary device copy of a host
 // table, and the grid placement of tiles that read the same rows.  Includable from .hip (the placement).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // wave_reduce.h -- device only: the pieces of float32 arithmetic and wave-level synchronisation that the row operators
-// (coherence.hip, coupling.hip, triggered.hip) prescribe in the same words.  Every function is one fixed sequence of
+// (coherence.hip, coupling.hip, triggered.hip, bandpass.hip) prescribe in the same words.  Every function is one fixed sequence of
 // correctly rounded operations; the kernels' own comments count the roundings.
 #pragma once
 #include <hip/hip_runtime.h>

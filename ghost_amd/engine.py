@@ -12,7 +12,8 @@ from . import _lib
 from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
-           "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "set_option",
+           "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
+           "bandpass", "band_rows", "band_weights", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -478,6 +479,135 @@ def triggered(result, cols, nb, na, rows=None):
         lambda ptr: check(lib.gcwt_triggered(result.buffer.ptr, result.pitch, c, s, n, rows[0], rows[1],
                                              arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, nb, na, ptr["amplitude"],
                                              ptr["power"], ptr["evoked"], ptr["vector"], ptr["itpc"], res.pitch)))
+
+
+def band_rows(bands, frequencies):
+    """The rows of bandpass() bands as a (B, 2) int32 array of (first, count): ``bands`` is one (f_lo, f_hi) pair or a
+    sequence of them, in Hz, closed intervals, each resolved as coupling_rows does.  The ValueError that anything else
+    raises names the band's index (``bands[k]``)."""
+    try:
+        one = not isinstance(bands, (str, bytes)) and len(bands) == 2 and all(np.ndim(v) == 0 and not isinstance(v, (str, bytes))
+                                                                             for v in bands)
+        seq = [bands] if one else list(bands)
+    except TypeError:
+        seq = None
+    if not seq:
+        raise ValueError("'bands' must be (f_lo, f_hi) in Hz or a non-empty sequence of such pairs, not %r" % (bands,))
+    return np.array([coupling_rows(b, frequencies, "bands[%d]" % k) for k, b in enumerate(seq)], dtype=np.int32).reshape(-1, 2)
+
+
+def _morlet_constants(w0):
+    """(K1, K2) = (pi^-1/4 sqrt(2 pi) int psi dv / v, 2 sqrt(pi) int psi^2 dv / v) with psi(v) = exp(-(v - w0)^2 / 2) -
+    exp(-w0^2 / 2 - v^2 / 2), by the midpoint rule on 2^19 cells of (0, w0 + 12] (psi / v stays finite at 0)."""
+    n = 1 << 19
+    v = (np.arange(n) + 0.5) * ((w0 + 12.0) / n)
+    psi = np.exp(-0.5 * (v - w0) ** 2) - np.exp(-0.5 * w0 ** 2 - 0.5 * v ** 2)
+    dv = (w0 + 12.0) / n
+    return (np.pi ** -0.25 * np.sqrt(2 * np.pi) * np.sum(psi / v) * dv, 2 * np.sqrt(np.pi) * np.sum(psi ** 2 / v) * dv)
+
+
+def band_weights(frequencies, wavelet):
+    """The weights (g, h) of bandpass() for the rows at ``frequencies`` (Hz, strictly monotonic, at least 2) of a
+    transform with ``wavelet`` (Morse or Morlet, its ``fs`` set for Morlet): float32 arrays of S entries, computed in
+    float64 and cast once.  Host only.  d_r is the cell of row r in ln f -- half the distance between its two neighbours,
+    the one-sided distance at either end of the grid: a property of the grid, not of a band.  The weights make a sinusoid
+    of amplitude A, well inside a band that spans the wavelet's response, read envelope = A and power = A^2:
+      Morse(gamma, beta), whose response peaks at 2, q = beta / gamma:  g_r = 2 d_r / C1,  h_r = 4 d_r / C2,
+        C1 = 2 e^q q^-q Gamma(q) / gamma,  C2 = 4 e^2q (2q)^-2q Gamma(2q) / gamma;
+      Morlet(w0), energy-normalised, sigma_r = (w0 + sqrt(2 + w0^2)) fs / (4 pi f_r) samples:
+        g_r = 2 d_r / (sqrt(sigma_r) K1),  h_r = 4 d_r / (sigma_r K2)  (K1, K2: _morlet_constants)."""
+    import math
+    from .wave import morlet, morse
+    f = np.asarray(frequencies, dtype=np.float64).ravel()
+    if f.size < 2:
+        raise ValueError("band_weights() needs at least 2 frequencies (a cell is the distance between neighbours), not %d" % f.size)
+    if not np.all(np.isfinite(f)) or np.any(f <= 0):
+        raise ValueError("the frequencies must be finite and positive")
+    step = np.diff(np.log(f))
+    if not (np.all(step > 0) or np.all(step < 0)):
+        raise ValueError("the frequencies must be strictly monotonic")
+    step = np.abs(step)
+    d = np.concatenate((step[:1], 0.5 * (step[:-1] + step[1:]), step[-1:]))
+    if isinstance(wavelet, morlet.Morlet):
+        w0 = float(wavelet.w0)
+        sigma = (w0 + np.sqrt(2 + w0 ** 2)) * float(wavelet.fs) / (4 * np.pi * f)
+        k1, k2 = _morlet_constants(w0)
+        g, h = 2 * d / (np.sqrt(sigma) * k1), 4 * d / (sigma * k2)
+    elif isinstance(wavelet, morse.Morse):
+        gamma, q = float(wavelet.gamma), float(wavelet.beta) / float(wavelet.gamma)
+        c1 = 2 * math.exp(q - q * math.log(q) + math.lgamma(q)) / gamma
+        c2 = 4 * math.exp(2 * q - 2 * q * math.log(2 * q) + math.lgamma(2 * q)) / gamma
+        g, h = 2 * d / c1, 4 * d / c2
+    else:
+        raise ValueError("band_weights() knows Morse and Morlet wavelets, not %r" % (wavelet,))
+    return g.astype(np.float32), h.astype(np.float32)
+
+
+_BAND_OUTPUTS = (("analytic", np.complex64), ("envelope", np.float32), ("power", np.float32))
+
+
+class BandpassResult(_RowOpResult):
+    """What bandpass() left on the device, each (C, B, N) with rows ``pitch`` elements apart in one DeviceBuffer and only
+    those of ``outputs``: ``analytic`` complex64, ``envelope`` and ``power`` float32; ``rows``: (B, 2) of (first, count).
+    ``to_host()`` brings them over; until ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr +
+    _offsets()[name]``."""
+
+    def __init__(self, buffer, n_channels, rows, n_cols, pitch, outputs):
+        self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), rows, tuple(outputs)
+        self.n_channels, self.n_bands, self.n_cols = int(n_channels), len(rows), int(n_cols)
+
+    def _planes(self):
+        lead = (self.n_channels, self.n_bands)
+        return tuple((name, dtype, lead) for name, dtype in _BAND_OUTPUTS if name in self.outputs), self.n_cols
+
+
+def _band_outputs(outputs):
+    names = [name for name, _ in _BAND_OUTPUTS]
+    seq = (outputs,) if isinstance(outputs, str) else outputs
+    try:
+        ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("'outputs' must name at least one of %s, each once, not %r" % (", ".join(names), outputs))
+    return tuple(seq)
+
+
+def _band_weight(w, n_scales, what, sign):
+    arr = np.asarray(w)
+    if arr.shape != (n_scales,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'%s' must hold one real weight for each of the result's %d rows" % (what, n_scales))
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if not np.all(np.isfinite(arr)) or (sign and np.any(arr < 0)):
+        raise ValueError("'%s' must be finite%s" % (what, " and at least 0" if sign else ""))
+    return arr
+
+
+def bandpass(result, rows, g, h, outputs=("analytic", "envelope", "power")):
+    """Band-limited analytic signals from the rows of a complex DeviceResult, computed where it lies (gcwt_bandpass;
+    include/ghostcwt.h has the definition): for every band of ``rows`` -- (B, 2) of (first, count) as band_rows returns
+    them; bands may overlap -- the sum of its rows weighted with ``g`` (analytic, envelope) and of their squared moduli
+    weighted with ``h`` (power), (S,) weights as band_weights returns them; the one that no output needs may be None.
+    Only the planes of ``outputs`` are allocated.  The result itself is only read.  -> BandpassResult, which stays on the
+    device until ``to_host()`` / ``free()``."""
+    c, s, n = _resident_complex(result, "bandpass", "a result sharded over several GPUs is not supported")
+    outputs = _band_outputs(outputs)
+    arr = np.asarray(rows)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("rows must be a (B, 2) integer array of (first, count) with B >= 1, not %s of shape %r" % (arr.dtype, arr.shape))
+    arr = np.array([_row_range((int(a), int(b)), s, "rows[%d]" % k) for k, (a, b) in enumerate(arr)], dtype=np.int32)
+    need_g, need_h = "analytic" in outputs or "envelope" in outputs, "power" in outputs
+    g = _band_weight(g, s, "g", False) if need_g else None
+    h = _band_weight(h, s, "h", True) if need_h else None
+    f32p = C.POINTER(C.c_float)
+    res = BandpassResult(None, c, arr, n, _pitch(n), outputs)
+    return _run_into(
+        res, "bandpass", "%d channels, %d bands, %d columns, %s" % (c, len(arr), n, " + ".join(outputs)),
+        "fewer bands or fewer outputs per call",
+        lambda ptr: check(lib.gcwt_bandpass(result.buffer.ptr, result.pitch, c, s, n, arr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            len(arr), None if g is None else g.ctypes.data_as(f32p),
+                                            None if h is None else h.ctypes.data_as(f32p), ptr.get("analytic"),
+                                            ptr.get("envelope"), ptr.get("power"), res.pitch)))
 
 
 def stride_columns(start, stop, stride):

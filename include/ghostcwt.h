@@ -268,6 +268,30 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
                    int64_t before, int64_t after,
                    float* d_amplitude, float* d_power, float* d_evoked, float* d_vector, float* d_itpc,
                    int64_t out_pitch);
+/* Band-limited analytic signals from the rows of a device-resident complex result, on the device that holds it
+ * (csrc/bandpass.hip): the weighted sum of a band's rows at every column, i.e. the inverse transform restricted to the
+ * band.  d_rows, pitch and n_cols are those of gcwt_coherence.  bands: n_bands (first, count) pairs in HOST memory, band
+ * k the rows first .. first + count - 1 = R rows inside [0, n_scales); bands may overlap and repeat.  g, h: n_scales
+ * float32 weights each in HOST memory, finite, h >= 0 (ghost_amd.engine.band_weights makes them so that a sinusoid of
+ * amplitude A well inside a band reads envelope = A and power = A^2).  The entry copies table and weights to the device
+ * and frees the copy.  For every channel c, band b and column t, with w_r = (re, im) = W[c][r][t], the rows taken in
+ * ascending r, each sum starting from an exact 0 and every operation a single correctly rounded float32 one:
+ *   x = fmaf(g[r], w_r.re, x)    y = fmaf(g[r], w_r.im, y)    p = fmaf(h[r], fmaf(w_r.im, w_r.im, w_r.re * w_r.re), p)
+ *   d_analytic [C][n_bands][n_cols]  complex64  (x, y)     (its angle: the band's phase)
+ *   d_envelope [C][n_bands][n_cols]  float32    sqrt(fmaf(y, y, x * x))
+ *   d_power [C][n_bands][n_cols]     float32    p
+ * The chain of a cell depends on its band's rows alone: a cell has the same bits asked for alone, among any other bands
+ * in any position of the list, for any column count, and on a second call.  Zero columns (the gaps between epochs) give
+ * exact zeros.  Rounding, with u = 2^-24 and T = sum |g_r| |w_r|: |analytic - exact| <= sqrt(2) R u T; envelope that plus
+ * 2 u |analytic|; power (2 + R) u relative.  Any output may be NULL, but not all; their rows are out_pitch (>= n_cols)
+ * elements apart.  g may be NULL if neither analytic nor envelope is asked for, h if power is not.  A band narrower than
+ * the wavelet's own response reads low, and the phase of analytic carries each row's sub-sample delay where the rows
+ * do: properties of the rows, not of the sum.  Plan-independent; the device is the one that holds d_rows.  Arguments --
+ * every band and weight among them -- are checked before any device call (GCWT_ERR_INVALID; the message names the
+ * first offending band's index). */
+int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                  const int32_t* bands, int32_t n_bands, const float* g, const float* h,
+                  float* d_analytic, float* d_envelope, float* d_power, int64_t out_pitch);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

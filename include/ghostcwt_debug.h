@@ -140,6 +140,17 @@ enum { GCWT_TRIGGERED_TILE_ROWS = 4, GCWT_TRIGGERED_TILE_LAGS = 64 };
 int gcwt_debug_triggered_grid(int32_t n_channels, int32_t n_rows, int64_t before, int64_t after, int32_t* n_row_tiles,
                               int64_t* n_lag_tiles, int64_t* n_blocks);
 
+/* Host only: the grid gcwt_bandpass launches for n_cols columns and n_bands bands.  The columns form tiles of
+ * GCWT_BANDPASS_TILE_COLS, counted from column 0, and the bands groups of GCWT_BANDPASS_GROUP_BANDS consecutive entries
+ * of the list (the last tile and the last group may be ragged); a workgroup takes one (channel, column tile, band
+ * group) and every row the group's bands hold.  n_blocks counts the workgroups: every band group of every (channel,
+ * column tile), the (channel, column tile)s padded to a multiple of 8 so that the band groups of one of them lie 8
+ * workgroups apart.  Any pointer may be NULL.  Returns GCWT_OK or an error code < 0 (a grid of more than 2^31 - 1
+ * workgroups among them). */
+enum { GCWT_BANDPASS_TILE_COLS = 512, GCWT_BANDPASS_GROUP_BANDS = 4 };
+int gcwt_debug_bandpass_grid(int32_t n_channels, int64_t n_cols, int32_t n_bands, int64_t* n_col_tiles,
+                             int32_t* n_band_groups, int64_t* n_blocks);
+
 #ifdef __cplusplus
 }
 #endif
