@@ -3,10 +3,11 @@
 // (transforms.py:203-204: convolve each epoch with each scale's kernel, keep abs.)
 //
 // k_synth7 pays one point of a 256-point inverse FFT for every stored sample.  Here a (block,
-// scale) goes through that transform only for q of its R phases (q = 2; 4 / 8 where R / 2 would
-// exceed the largest interpolation factor) -- the scale's complex output z at q x the level's
+// scale) goes through that transform only for q of its R phases (q = 2 at R = 16, q = 4 from R = 32 up, and the
+// planner doubles q while R / q would exceed the largest interpolation factor, kInterpMaxFactor = 1024: q = 8 at
+// R = 8192, q = 16 at R = 16384, planner.cpp: design_interp_level) -- the scale's complex output z at q x the level's
 // rate, demodulated to its band centre so that it is a low-pass signal -- and the R / q = I
-// samples between two of those come from an 8-tap (q = 2) or 6-tap (q = 4) polyphase FIR with real coefficients
+// samples between two of those come from an 8-tap (q = 2, or q = 4 where six miss the bound) or 6-tap (q >= 4) polyphase FIR with real coefficients
 // (interp.h: minimax design under the envelope of the level's gains; what it adds is bounded per
 // level from the scales' own gains, planner.cpp: plan_interp_level, and stays below 2e-7 of a
 // scale's peak).  |.| does not see the demodulation.  Per stored sample: 8 packed FMAs + |.|
@@ -54,7 +55,8 @@ constexpr int kWavesI = kThreadsI / 64;
 constexpr int kPlaneI = kThreadsI + 1;
 constexpr int kZPad = 4;                         // v2f entries between the slots of the z buffer: their
                                                  // writes fall on different banks
-constexpr int kSlotsMax = kColsI / 2;            // z slots and scale slots of a pass: q >= 2
+constexpr int kSlotsMax = kColsI / 2;            // z slots and scale slots of a pass: q >= 2 (q = 16: ns = 1 and one z
+                                                 // slot of 4096 + kZPad entries, which kZElems covers)
 static_assert(kColsI == kInterpCols, "the host cuts the passes for this many columns (interp.h)");
 constexpr int kZElems = 256 * kColsI + kSlotsMax * kZPad;     // z buffer
 constexpr int kExElems = kZElems > 16 * kPlaneI ? kZElems : 16 * kPlaneI;   // ... in place of the 16 exchange planes

@@ -76,10 +76,19 @@ def low_cut(theta_cut, p_big, m):
     return 0.5 - 0.5 * np.cos(np.pi * u)
 
 
+def level_of_scale(plan):
+    """Index into ``plan.debug_levels()`` of every scale (-1: not on a decimated level).  Two levels may share a
+    decimation (heavy tails: a second level with a longer halo), so the halo tells them apart."""
+    si = plan.scale_info()
+    key = {(lv["decimation"], lv["halo"]): l for l, lv in enumerate(plan.debug_levels())}
+    return np.array([key.get((int(r), int(h)), -1) if m == 0 else -1
+                     for m, r, h in zip(si["method"], si["decimation"], si["halo"])])
+
+
 def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=256, plan=None,
-                  normalization="bandpass", order=0):
+                  normalization="bandpass", order=0, rows=None):
     """Model output, complex128 (S, N).  ``plan``: a CwtPlan for the same layout (made
-    here when omitted; planning needs no GPU)."""
+    here when omitted; planning needs no GPU).  ``rows``: only these scales (the others stay zero)."""
     from ghost_amd.engine import CwtPlan
     x = np.asarray(x).squeeze().astype(np.float64)
     x = x - x.mean()
@@ -91,8 +100,7 @@ def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=25
         plan = CwtPlan(n, 1, fs, freqs_hz, gamma=gamma, beta=beta, epoch_bounds=epoch_bounds,
                        normalization=normalization, order=order)
     si = plan.scale_info()
-    shift_of = {lv["decimation"]: lv["band_shift"] for lv in plan.debug_levels()}
-    cut_of = {lv["decimation"]: lv["low_cut"] for lv in plan.debug_levels()}
+    levels, level_of = plan.debug_levels(), level_of_scale(plan)
     omegas = orc.hz_to_rad(freqs_hz, fs)
     lengths = orc.morse_lengths(omegas, gamma, beta)
     assert np.array_equal(lengths, si["length"])
@@ -105,6 +113,8 @@ def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=25
         X = fft(np.concatenate([np.zeros(lead), x[start:stop]]), n=p_big)
         xr_cache = {}
         for i, (om, L) in enumerate(zip(omegas, lengths)):
+            if rows is not None and i not in rows:
+                continue
             method = si["method"][i]
             if method in (1, 3):                     # time domain / block convolution: the literal kernel
                 psi, _ = orc.morse_kernel(L, om, gamma, beta, normalization, order)
@@ -117,14 +127,15 @@ def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=25
                 continue
             R, lh, hop = int(si["decimation"][i]), int(si["halo"][i]), int(si["hop"][i])
             M = p_big // R
-            shift = shift_of[R]
-            if R not in xr_cache:
+            lvl = levels[level_of[i]]
+            shift = lvl["band_shift"]
+            if level_of[i] not in xr_cache:
                 U = shift * M // B
                 sl = X[(np.arange(M) - U) % p_big]
                 if not shift:
-                    sl = sl * low_cut(cut_of[R], p_big, M)
-                xr_cache[R] = ifft(sl) / R                                 # the engine's x_R: bin u is frequency u - U
-            xr = xr_cache[R]
+                    sl = sl * low_cut(lvl["low_cut"], p_big, M)
+                xr_cache[level_of[i]] = ifft(sl) / R                       # the engine's x_R: bin u is frequency u - U
+            xr = xr_cache[level_of[i]]
             k = np.arange(B)
             H = exact_response(2 * np.pi * (k - shift) / (B * R), om, L, gamma, beta, normalization, order)
             tw = np.exp(2j * np.pi * np.outer(k - shift, np.arange(R)) / (B * R))
@@ -141,11 +152,14 @@ def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=25
     return out
 
 
-def amplitude_interpolated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=256, plan=None):
+def amplitude_interpolated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=256, plan=None,
+                           host_gain_from=None):
     """|W| (S, N) float64 the way the engine makes it for amplitude output: the levels the
     planner designed an interpolator for (``plan.debug_interp()``) through q phases + the 8-tap
     FIR with the planner's own float32 coefficients and demodulation bins, every other scale
-    as in ``cwt_decimated``.  Whole epochs only."""
+    as in ``cwt_decimated``.  Whole epochs only.  ``host_gain_from``: kernels of at least that many taps take G
+    from ``plan.debug_exact_gain`` (the library's host evaluation of the same closed form) instead of the NumPy
+    ``exact_gain``, which is slow there."""
     from ghost_amd.engine import CwtPlan
     x = np.asarray(x).squeeze().astype(np.float64)
     n = x.size
@@ -154,11 +168,11 @@ def amplitude_interpolated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=2
     freqs_hz = np.atleast_1d(np.asarray(freqs_hz, dtype=np.float64))
     if plan is None:
         plan = CwtPlan(n, 1, fs, freqs_hz, gamma=gamma, beta=beta, epoch_bounds=epoch_bounds, output="amplitude")
-    out = np.abs(cwt_decimated(x, fs, freqs_hz, epoch_bounds, gamma, beta, B, plan=plan))
     si, di, levels = plan.scale_info(), plan.debug_interp(), plan.debug_levels()
-    by_r = {lv["decimation"]: d for lv, d in zip(levels, di["levels"])}
-    shift_of = {lv["decimation"]: lv["band_shift"] for lv in levels}
-    cut_of = {lv["decimation"]: lv["low_cut"] for lv in levels}
+    level_of = level_of_scale(plan)
+    designed = [i for i in range(len(freqs_hz)) if level_of[i] >= 0 and di["levels"][level_of[i]] is not None]
+    plain = set(range(len(freqs_hz))) - set(designed)
+    out = np.abs(cwt_decimated(x, fs, freqs_hz, epoch_bounds, gamma, beta, B, plan=plan, rows=plain))
     omegas = orc.hz_to_rad(freqs_hz, fs)
     xc = x - x.mean()
     fft_len = {(a, b): p for (a, b, p) in plan.segments()}
@@ -168,23 +182,28 @@ def amplitude_interpolated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=2
         p_big = fft_len[(start, stop)]
         lead = start - (start & ~63)
         X = fft(np.concatenate([np.zeros(lead), xc[start:stop]]), n=p_big)
+        xr_cache = {}
         for i, (om, L) in enumerate(zip(omegas, si["length"])):
-            R = int(si["decimation"][i])
-            d = by_r.get(R) if si["method"][i] == 0 else None
-            if d is None:
+            if i not in designed:
                 continue
+            R, lvl, d = int(si["decimation"][i]), levels[level_of[i]], di["levels"][level_of[i]]
             q, I, lh, hop = d["q"], d["factor"], int(si["halo"][i]), int(si["hop"][i])
             coef = d["coef"][1 if int(L) % 2 == 0 else 0].astype(np.float64)   # [I][8]
             kc = int(di["demod"][i])
             assert kc % q == 0, (kc, q)
             M = p_big // R
-            shift = shift_of[R]
-            sl = X[(np.arange(M) - shift * M // B) % p_big]
-            if not shift:
-                sl = sl * low_cut(cut_of[R], p_big, M)
-            xr = ifft(sl) / R
+            shift = lvl["band_shift"]
+            if level_of[i] not in xr_cache:
+                sl = X[(np.arange(M) - shift * M // B) % p_big]
+                if not shift:
+                    sl = sl * low_cut(lvl["low_cut"], p_big, M)
+                xr_cache[level_of[i]] = ifft(sl) / R
+            xr = xr_cache[level_of[i]]
             k = np.arange(B)
-            G = exact_gain(2 * np.pi * (k - shift) / (B * R), om, int(L), gamma, beta)
+            if host_gain_from is not None and int(L) >= host_gain_from:
+                G = plan.debug_exact_gain(i, k - shift, B * R)
+            else:
+                G = exact_gain(2 * np.pi * (k - shift) / (B * R), om, int(L), gamma, beta)
             tw = np.exp(2j * np.pi * np.outer(k, np.arange(q)) / (B * q))            # phase p of bin k
             demod = np.exp(-2j * np.pi * kc * np.arange(B * q) / (B * q))           # bins counted from k_c
             nblk = int(math.ceil(math.ceil((lead + ne) / R) / hop))
