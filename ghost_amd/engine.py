@@ -922,7 +922,9 @@ class CwtPlan:
     def debug_fetch(self, what, channel=0, epoch=0, level=0):
         lv = self.debug_levels(epoch)
         if what == 0:
-            n = self.info["fft_length"]
+            # the STORED spectrum of the segment: its FFT length, or 2^22 bins of it in long mode (planner.h: p_store)
+            p = self.segments()[epoch][2]
+            n = p // max(1, p >> 22)
         elif what == 1:
             n = lv[level]["m"]
         else:

@@ -76,6 +76,19 @@ def low_cut(theta_cut, p_big, m):
     return 0.5 - 0.5 * np.cos(np.pi * u)
 
 
+def level_input(X, lvl, B=256):
+    """x_R of one level (an entry of ``debug_levels``) from the segment's spectrum X (P bins, natural order), as
+    ``cwt_decimated`` uses it: the level's M bins from U = shift M / B below zero frequency on, its low cut, the
+    inverse transform of M points, over R.  Bin u of the slice is frequency u - U."""
+    p_big, shift = X.size, int(lvl["band_shift"])
+    M = p_big // int(lvl["decimation"])
+    U = shift * M // B
+    sl = X[(np.arange(M) - U) % p_big]
+    if not shift:
+        sl = sl * low_cut(lvl["low_cut"], p_big, M)
+    return ifft(sl) / (p_big // M)
+
+
 def level_of_scale(plan):
     """Index into ``plan.debug_levels()`` of every scale (-1: not on a decimated level).  Two levels may share a
     decimation (heavy tails: a second level with a longer halo), so the halo tells them apart."""
@@ -130,11 +143,7 @@ def cwt_decimated(x, fs, freqs_hz, epoch_bounds=None, gamma=3.0, beta=20.0, B=25
             lvl = levels[level_of[i]]
             shift = lvl["band_shift"]
             if level_of[i] not in xr_cache:
-                U = shift * M // B
-                sl = X[(np.arange(M) - U) % p_big]
-                if not shift:
-                    sl = sl * low_cut(lvl["low_cut"], p_big, M)
-                xr_cache[level_of[i]] = ifft(sl) / R                       # the engine's x_R: bin u is frequency u - U
+                xr_cache[level_of[i]] = level_input(X, lvl, B)
             xr = xr_cache[level_of[i]]
             k = np.arange(B)
             H = exact_response(2 * np.pi * (k - shift) / (B * R), om, L, gamma, beta, normalization, order)
