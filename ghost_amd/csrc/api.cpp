@@ -63,6 +63,7 @@ struct EpochDev {
   SynthiItem* items_i = nullptr;     // interpolating kernel (synthi.hip)
   SynthiLevel* levels_i = nullptr;
   int n_items_i = 0;
+  int split_i = 0;                   // items_i[0 .. split_i): the levels below gcwt_plan::interp_split_r, launched first (run_pipeline)
   SynthpItem* items_p[2] = {nullptr, nullptr};   // pipelined interpolating kernel (synthp.hip); [1]: levels with I = 4
   SynthpLevel* levels_p = nullptr;
   int n_items_p[2] = {0, 0};
@@ -120,6 +121,13 @@ struct gcwt_plan {
   bool synth_streams = false; // GHOSTCWT_SYNTH_STREAMS=1: the interpolating kernel runs beside k_synth7 on aux[0] (its store-bound
                               // workgroups share the CUs with the arithmetic-bound ones: measured equal on the headline,
                               // profiles/r03_synth_study.md); default: one after the other, so that per-kernel times add up
+  int interp_split_r = 64;    // option interp_split_r: k_synthi's items of the levels below this decimation are a launch of their
+                              // own, made first: the cycle-bound levels (R = 16, 32: profiles/r06_bound.md 3) apart from the
+                              // store-bound ones.  In one launch workgroups of both kinds share the CUs and k_synthi takes
+                              // 0.23 ms of 6.4 longer (profiles/early_interp.md); 0: one launch
+  bool early_interp = false;  // option early_interp = 1: the level passes k_synthi reads run on the plan's stream with k_synthi right
+                              // behind them, the others on aux[] beside it, joined in front of the first kernel that reads them
+                              // (run_pipeline).  Measured: the passes leave the critical path and k_synthi grows by as much; off
   hipStream_t cur = nullptr;  // the stream the stage in hand is launched on (profiling spans follow it)
   // workspace
   bool high_precision = true; // gcwt_params.precision: float64 forward transform (fwd64.hip) + per-level low cut
@@ -438,6 +446,8 @@ static int gcwt_plan_create_impl(gcwt_plan** out, const gcwt_params* params) {
   if (option_is_set("interp_grid")) p->interp_grid = option_or("interp_grid", 0) != 0;
   p->synth_streams = option_or("synth_streams", 0) != 0;
   p->fold_mean = option_or("fold_mean", 1) != 0;
+  p->early_interp = option_or("early_interp", 0) != 0;
+  p->interp_split_r = (int)std::min<long long>(1 << 30, std::max<long long>(0, option_or("interp_split_r", 64)));
   p->interp_lgnb = (int)option_or("interp_lgnb", -1);
   p->use_synthp = kMeasureBuild && option_or("synthp", 0) != 0;   // (the kernel exists in the measure build only)
   p->synthp_lgnb = (int)option_or("synthp_lgnb", -1);
@@ -883,10 +893,18 @@ static int gcwt_plan_upload_impl(gcwt_plan* p) {
       }
       std::vector<size_t> order(items_i.size());
       for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-      std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return item_bytes[x] > item_bytes[y]; });
+      // one array in two parts, the levels below interp_split_r first, each part largest first; the parts are a
+      // launch each (run_pipeline).  interp_split_r = 0: the first part is empty, one list, one launch.
+      const int split_r = p->interp_split_r;
+      std::vector<char> late(items_i.size());
+      for (size_t i = 0; i < late.size(); ++i) late[i] = hp.levels[(size_t)items_i[i].level].decimation >= split_r;
+      std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+        return late[x] != late[y] ? late[x] < late[y] : item_bytes[x] > item_bytes[y];
+      });
       std::vector<SynthiItem> sorted(items_i.size());
       for (size_t i = 0; i < order.size(); ++i) sorted[i] = items_i[order[i]];
       items_i.swap(sorted);
+      p->ep_dev[e].split_i = (int)std::count(late.begin(), late.end(), (char)0);
     }
     p->ep_dev[e].n_items_i = (int)items_i.size();
     if ((rc = upload_vec(&p->ep_dev[e].items_i, items_i, p->stream))) return bail(rc);
@@ -1190,15 +1208,35 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
     // the headline's R = 2 level is half of all the work and keeps a stream to itself) -- and
     // join before the synthesis.
     const bool side = p->level_streams && hp.levels.size() > 2;
+    const EpochDev& dev = p->ep_dev[ep.batch_first];
+    // The interpolating kernel reads the x_R of its own levels only (R >= 16: an eighth of the level passes' traffic)
+    // and the kernels behind it read the rest.  Option early_interp = 1: group H, the levels whose x_R an interpolated
+    // level reads, on the plan's own stream with k_synthi right behind them; group L, the others, on aux[0] and aux[1]
+    // beside both, joined in front of the first kernel that reads them.  Off by default: what the front end loses
+    // k_synthi gains, and no step is shorter for it (profiles/early_interp.md).  Never with every stage between events
+    // (profiling level 1: stages_ms stays what it was), with synth_streams (k_synthi on aux[0]) or without an
+    // interpolated level.
+    std::vector<char> in_h(hp.levels.size(), 0);
+    bool any_h = false;
+    for (size_t l = 0; l < hp.levels.size(); ++l)
+      if (level_kernel(p, hp.levels[l]) == LK_INTERP) {
+        in_h[hp.levels[l].xr_owner >= 0 ? (size_t)hp.levels[l].xr_owner : l] = 1;
+        any_h = true;
+      }
+    for (size_t l = 0; l < hp.levels.size(); ++l)              // a level that shares an x_R follows its owner
+      if (hp.levels[l].xr_owner >= 0) in_h[l] = in_h[(size_t)hp.levels[l].xr_owner];
+    const bool early = side && p->early_interp && p->profiling != 1 && !p->synth_streams && any_h &&
+                       dev.n_items_i + dev.n_items_p[0] + dev.n_items_p[1] > 0;
     std::vector<int> stream_of(hp.levels.size(), 0);
     if (side) {
       double load[3] = {0.0, 0.0, 0.0};
       std::vector<size_t> order;
       for (size_t l = 0; l < hp.levels.size(); ++l)
-        if (hp.levels[l].xr_owner == (int)l) order.push_back(l);
+        if (hp.levels[l].xr_owner == (int)l && !(early && in_h[l])) order.push_back(l);
       std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ep.lv[a].m > ep.lv[b].m; });
+      const int k0 = early ? 1 : 0;        // (early: the plan's own stream is group H's)
       for (size_t l : order) {
-        const int k = (int)(std::min_element(load, load + 3) - load);
+        const int k = (int)(std::min_element(load + k0, load + 3) - load);
         stream_of[l] = k;
         load[k] += 40e-6 + 32.0 * (double)ep.lv[l].m * (double)slots / 4.5e12;   // seconds
       }
@@ -1212,7 +1250,10 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       he = hipEventRecord(spectrum_ready, st);
       if (he != hipSuccess) return hip_err(he, "hipEventRecord");
     }
-    for (size_t l = 0; l < hp.levels.size(); ++l) {
+    // (early: group H's passes are launched first, in level order, then group L's)
+    for (size_t li = 0; li < (early ? 2 : 1) * hp.levels.size(); ++li) {
+      const size_t l = li % hp.levels.size();
+      if (early && (in_h[l] != 0) != (li < hp.levels.size())) continue;
       const LevelPlan& lp = hp.levels[l];
       const EpochLevel& el = ep.lv[l];
       float2* xr = p->d_xr + el.xr_offset;
@@ -1267,10 +1308,12 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
         RUN(ST_BLOCK, launch_block_fft(xr, p->d_xb + el.xb_offset, el.m, lp.hop, lp.halo, el.blk_lo,
                                        el.nblk, hp.max_xr, hp.max_xb, p->d_tw256, scale, slots, ls));
     }
-    if (side) {
-      p->cur = nullptr;
+    if (side) p->cur = nullptr;
+    // the plan's stream waits for the level passes on aux[]: before the synthesis, or (early) behind k_synthi's launches
+    auto join_levels = [&]() -> int {
       for (int k = 0; k < 2; ++k) {
         if (!forked[k]) continue;
+        forked[k] = false;
         hipEvent_t done;
         int rc_ = get_event(p, &done);
         if (rc_) return rc_;
@@ -1278,8 +1321,12 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
         if (he == hipSuccess) he = hipStreamWaitEvent(st, done, 0);
         if (he != hipSuccess) return hip_err(he, "level streams join");
       }
+      return GCWT_OK;
+    };
+    if (!early) {
+      int rc_ = join_levels();
+      if (rc_) return rc_;
     }
-    const EpochDev& dev = p->ep_dev[ep.batch_first];
     // The interpolating kernel is launched first; with GHOSTCWT_SYNTH_STREAMS=1 on a stream of its own, k_synth7 beside it:
     // the two share the CUs (store-bound workgroups next to arithmetic-bound ones) and each
     // fills the other's tail.  Both only read what the level passes left and write disjoint rows.
@@ -1319,8 +1366,15 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       if (dev.n_items_i > 65535) ai.channels_fastest = 0;       // (grid.y is 16 bits wide)
       ai.seg = sout;
       p->cur = si;
-      if (strided) RUN(ST_INTERP, launch_synthis(mode, ai, dev.n_items_i, slots, si));
-      else RUN(ST_INTERP, launch_synthi(mode, ai, dev.n_items_i, slots, si));
+      // two launches, one behind the other: the levels below interp_split_r, then the rest (gcwt_plan_upload: one
+      // list in two parts)
+      for (int part = 0; part < 2; ++part) {
+        const int first = part == 0 ? 0 : dev.split_i, n_part = part == 0 ? dev.split_i : dev.n_items_i - dev.split_i;
+        if (n_part == 0) continue;
+        ai.items = dev.items_i + first;
+        if (strided) RUN(ST_INTERP, launch_synthis(mode, ai, n_part, slots, si));
+        else RUN(ST_INTERP, launch_synthi(mode, ai, n_part, slots, si));
+      }
       p->cur = nullptr;
     }
     for (int k = 0; k < 2; ++k) {
@@ -1353,6 +1407,10 @@ static int run_pipeline(gcwt_plan* p, const float* dx, float* dout, int64_t r0, 
       return set_err(GCWT_ERR_INVALID, "internal: a level planned for the measure build's pipelined kernel");
 #endif
       p->cur = nullptr;
+    }
+    if (early) {                           // every kernel from here on may read a level of group L; so may the next batch
+      int rc_ = join_levels();             // (d_x, d_xr and d_xs are reused)
+      if (rc_) return rc_;
     }
     if (dev.n_items > 0) {
       SynthArgs a{};
