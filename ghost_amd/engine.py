@@ -13,7 +13,7 @@ from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
            "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
-           "bandpass", "band_rows", "band_weights", "set_option",
+           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "event_filter", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -608,6 +608,120 @@ def bandpass(result, rows, g, h, outputs=("analytic", "envelope", "power")):
                                             len(arr), None if g is None else g.ctypes.data_as(f32p),
                                             None if h is None else h.ctypes.data_as(f32p), ptr.get("analytic"),
                                             ptr.get("envelope"), ptr.get("power"), res.pitch)))
+
+
+def _traces(buffer_ptr, pitch, n_traces, n_cols, what):
+    """(pointer, pitch, n_traces, n_cols) of float32 traces on the device as the C entries take them."""
+    ptr = buffer_ptr if isinstance(buffer_ptr, C.c_void_p) else C.c_void_p(buffer_ptr)
+    if not ptr:
+        raise ValueError("%s() needs traces on the device: the buffer has been freed" % what)
+    for name, v in (("pitch", pitch), ("n_traces", n_traces), ("n_cols", n_cols)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s() takes '%s' as an integer, not %r" % (what, name, v))
+    return ptr, int(pitch), int(n_traces), int(n_cols)
+
+
+def trace_stats(buffer_ptr, pitch, n_traces, n_cols):
+    """Per-trace statistics of float32 traces on the device -- ``n_traces`` rows of ``n_cols`` live columns, ``pitch``
+    elements apart, at ``buffer_ptr`` (a c_void_p or an address) -- over the columns that are not exactly 0
+    (gcwt_trace_stats; include/ghostcwt.h has the definition and the order of the float64 sums).  -> (n int64, mean
+    float64, sd float64), each (n_traces,); mean and sd are 0 where n is.  Three numbers per trace cross to the host."""
+    ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_stats")
+    n, mean, sd = np.zeros(max(n_traces, 0), np.int64), np.zeros(max(n_traces, 0)), np.zeros(max(n_traces, 0))
+    f64p = C.POINTER(C.c_double)
+    check(lib.gcwt_trace_stats(ptr, pitch, n_traces, n_cols, n.ctypes.data_as(C.POINTER(C.c_int64)), mean.ctypes.data_as(f64p),
+                               sd.ctypes.data_as(f64p)))
+    return n, mean, sd
+
+
+_RUN_FIELDS = (("start", np.int64), ("stop", np.int64), ("peak_col", np.int64), ("peak", np.float32))
+
+
+def trace_runs(buffer_ptr, pitch, n_traces, n_cols, lo):
+    """The maximal runs of columns above ``lo`` -- (n_traces,) finite thresholds, one per trace -- of float32 traces on
+    the device, with their peaks (gcwt_trace_runs; include/ghostcwt.h has the definition): found and compacted on the
+    device, sized by a first call and written by a second into device arrays that are freed again.  -> dict of host
+    arrays over the runs, ordered by trace and then by start: ``trace`` int64, ``start``, ``stop`` int64 (the run is
+    the columns [start, stop)), ``peak_col`` int64 (the first column that holds the largest value), ``peak`` float32;
+    and ``counts`` (n_traces,) int64: the runs of each trace.  28 bytes per run cross to the host."""
+    ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_runs")
+    arr = np.asarray(lo)
+    if arr.shape != (n_traces,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'lo' must hold one real threshold for each of the %d traces" % n_traces)
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    counts = np.zeros(n_traces, np.int64)
+    i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+
+    def call(capacity, where):
+        check(lib.gcwt_trace_runs(ptr, pitch, n_traces, n_cols, arr.ctypes.data_as(f32p), capacity, where["start"], where["stop"],
+                                  where["peak_col"], where["peak"], counts.ctypes.data_as(i64p)))
+
+    call(0, dict.fromkeys((name for name, _ in _RUN_FIELDS)))
+    total = int(counts.sum())
+    out = {"trace": np.repeat(np.arange(n_traces, dtype=np.int64), counts)}
+    if total == 0:
+        out.update((name, np.zeros(0, dtype)) for name, dtype in _RUN_FIELDS)
+    else:
+        nbytes = sum(total * np.dtype(dtype).itemsize for _, dtype in _RUN_FIELDS)
+        free, _ = device_memory()
+        if nbytes > free:
+            raise MemoryError("trace_runs() needs %d bytes on the device for %d runs and %d are free: a higher threshold"
+                              % (nbytes, total, free))
+        buf = DeviceBuffer(nbytes)
+        try:
+            offsets, end = {}, 0
+            for name, dtype in _RUN_FIELDS:                 # (the int64 arrays first: each starts on 8 bytes)
+                offsets[name] = end
+                end += total * np.dtype(dtype).itemsize
+            sized = counts.copy()
+            call(total, {name: C.c_void_p(buf.ptr.value + off) for name, off in offsets.items()})
+            if not np.array_equal(sized, counts):
+                raise RuntimeError("trace_runs(): the traces changed between the two calls")
+            out.update((name, buf.download((total,), dtype, offsets[name])) for name, dtype in _RUN_FIELDS)
+        finally:
+            buf.free()
+    out["counts"] = counts
+    return out
+
+
+def event_filter(trace, start, stop, peak_col, peak, hi, time_of_col, min_gap, min_duration, max_duration, period):
+    """From the runs above the edge threshold (as trace_runs returns them: ordered by trace, then by start) to events.
+    Pure NumPy on the compact list, in this order:
+      1. keep the runs with ``peak > hi[trace]`` (``hi``: one threshold per trace);
+      2. within a trace, merge neighbours whose gap time[start_next] - time[stop_prev - 1] is < ``min_gap`` seconds: the
+         merged event spans both, its peak is the larger one, the earlier on a tie.  ``time_of_col``: the columns' times
+         on the recording's clock, so that a gap between epochs counts with its real length (None: column j at j
+         ``period``);
+      3. drop the events whose duration (stop - start) ``period`` is below ``min_duration`` or above ``max_duration``
+         (None: no upper limit); ``period``: seconds per column, K / fs.
+    -> dict of ``trace``, ``start``, ``stop``, ``peak_col`` (int64) and ``peak`` (float32)."""
+    trace, start, stop, peak_col = (np.asarray(v, dtype=np.int64).ravel() for v in (trace, start, stop, peak_col))
+    peak = np.asarray(peak, dtype=np.float32).ravel()
+    hi = np.atleast_1d(np.asarray(hi, dtype=np.float32))
+    if not (trace.size == start.size == stop.size == peak_col.size == peak.size):
+        raise ValueError("event_filter(): trace, start, stop, peak_col and peak must have one entry per run")
+    min_gap, min_duration, period = _seconds(min_gap, "min_gap"), _seconds(min_duration, "min_duration"), float(period)
+    max_duration = None if max_duration is None else _seconds(max_duration, "max_duration")
+    keep = peak > hi[trace] if trace.size else np.zeros(0, bool)
+    trace, start, stop, peak_col, peak = trace[keep], start[keep], stop[keep], peak_col[keep], peak[keep]
+    if trace.size > 1 and min_gap > 0:
+        if time_of_col is None:
+            gap = (start[1:] - (stop[:-1] - 1)) * period
+        else:
+            t = np.asarray(time_of_col, dtype=np.float64).ravel()
+            gap = t[start[1:]] - t[stop[:-1] - 1]
+        joined = (trace[1:] == trace[:-1]) & (gap < min_gap)
+        first = np.flatnonzero(np.concatenate(([True], ~joined)))            # the first run of every event
+        last = np.concatenate((first[1:], [trace.size])) - 1
+        top = np.maximum.reduceat(peak, first)
+        group = np.cumsum(np.concatenate(([True], ~joined))) - 1
+        at = np.minimum.reduceat(np.where(peak == top[group], np.arange(trace.size), trace.size), first)
+        trace, start, stop, peak_col, peak = trace[first], start[first], stop[last], peak_col[at], top
+    duration = (stop - start) * period
+    keep = duration >= min_duration
+    if max_duration is not None:
+        keep &= duration <= max_duration
+    return {"trace": trace[keep], "start": start[keep], "stop": stop[keep], "peak_col": peak_col[keep], "peak": peak[keep]}
 
 
 def stride_columns(start, stop, stride):

@@ -64,6 +64,20 @@ class _Bandpass:
         self.bands, self.rows, self.frequencies, self.time = bands, rows, frequencies, time
 
 
+class _Events:
+    """What ContinuousWaveletTransform.detect returns (host arrays)."""
+
+    def __init__(self, events, per_channel, band, rows, frequencies, on):
+        self.channel, self.start, self.stop, self.peak_time, self.peak = (events[k] for k in ("channel", "start", "stop", "peak_time", "peak"))
+        self.start_col, self.stop_col, self.peak_col = events["start_col"], events["stop_col"], events["peak_col"]
+        self.mean, self.sd, self.lo, self.hi = (per_channel[k] for k in ("mean", "sd", "lo", "hi"))
+        self.n_columns, self.n_candidates = per_channel["n_columns"], per_channel["n_candidates"]
+        self.band, self.rows, self.frequencies, self.on = band, rows, frequencies, on
+
+    def __len__(self):
+        return len(self.channel)
+
+
 class ContinuousWaveletTransform(WaveletTransform):
     """Continuous wavelet transform.
 
@@ -505,6 +519,90 @@ class ContinuousWaveletTransform(WaveletTransform):
         return _Bandpass(out.get("analytic"), out.get("envelope"), out.get("power"),
                          np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
                          [f[a:a + n] for a, n in rows], None if t is None else np.asarray(t))
+
+    def detect(self, band, *, on="envelope", threshold=3.0, edge=0.0, units="sd", min_duration=0.0, max_duration=None,
+               min_gap=0.0):
+        """Threshold-crossing events of one band of the last transform -- ripples, spindles, bursts: the times that
+        ``triggered()`` takes --, found on the device.  The transform must have been ``output='complex'`` on one
+        device.  ``band``: one (f_lo, f_hi) pair in Hz, its rows and weights those of ``bandpass()``; ``on``:
+        'envelope' or 'power', the band trace of ``bandpass()`` that is thresholded.  The trace stays on the device:
+        per channel its mean and sd over the columns that are not exactly 0 (the gaps between epochs) are taken there,
+        then the maximal runs of columns with trace > lo and the largest value of each (include/ghostcwt.h:
+        gcwt_trace_stats, gcwt_trace_runs), and only those runs cross to the host, 28 bytes each.  ``units='sd'``: hi
+        = mean + ``threshold`` sd and lo = mean + ``edge`` sd per channel; ``units='absolute'``: hi = ``threshold``
+        and lo = ``edge`` in the trace's units; both rounded to float32 once, and finite hi >= lo >= 0 is required
+        (lo >= 0 is what makes the exact zeros of a gap split runs).  An event is a run whose peak is > hi (the double
+        threshold: lo sets its boundaries, hi decides); then neighbours in a channel less than ``min_gap`` seconds
+        apart -- from the last column of one to the first of the next on the clock of ``time``, so a gap between
+        epochs counts with its real length -- are merged, and events shorter than ``min_duration`` or longer than
+        ``max_duration`` seconds (columns x K / fs with the output stride K) are dropped (engine.event_filter).  The
+        returned object has flat arrays over the events, ordered by channel and then by time: ``channel``, ``start``
+        and ``stop`` (seconds: the times of the first and of the last column above lo), ``peak_time``, ``peak``
+        (float32: the trace's value there, the first of equal ones), ``start_col``, ``stop_col`` (one past the last
+        column) and ``peak_col``; per channel ``mean``, ``sd`` (float64), ``lo``, ``hi`` (float32: the values
+        compared with), ``n_columns`` (the non-zero columns) and ``n_candidates`` (the runs above lo, before any
+        filtering); and ``band``, ``rows`` (first, count), ``frequencies`` and ``on``.  After the reference's
+        single-channel call the per-channel items lose their axis.  ``r.peak_time[r.channel == c]`` is what
+        ``triggered()`` takes.  The runs and their peaks are exact, so the events are those of the same definition
+        applied to ``bandpass()``'s trace on the host, bit for bit.  The resident result, ``fetch()`` and the result
+        attributes are untouched."""
+        from .. import engine
+        result, squeeze = self._resident_rows("detect")
+        if not isinstance(on, str) or on not in ("envelope", "power"):
+            raise ValueError("detect(): 'on' must be 'envelope' or 'power', not %r" % (on,))
+        if not isinstance(units, str) or units not in ("sd", "absolute"):
+            raise ValueError("detect(): 'units' must be 'sd' or 'absolute', not %r" % (units,))
+        for name, v in (("threshold", threshold), ("edge", edge)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+                raise ValueError("detect(): '%s' must be a finite number, not %r" % (name, v))
+        threshold, edge = float(threshold), float(edge)
+        if threshold < edge:
+            raise ValueError("detect(): hi < lo: 'threshold' (%g) is below 'edge' (%g)" % (threshold, edge))
+        if units == "absolute":
+            with np.errstate(over="ignore"):
+                hi1, lo1 = np.float32(threshold), np.float32(edge)
+            if not np.isfinite(hi1):
+                raise ValueError("detect(): hi = %g is not finite in float32" % threshold)
+            if lo1 < 0:
+                raise ValueError("detect(): lo < 0: 'edge' (%g) must be at least 0, the value of a gap between epochs" % edge)
+        min_gap, min_duration = engine._seconds(min_gap, "min_gap"), engine._seconds(min_duration, "min_duration")
+        max_duration = None if max_duration is None else engine._seconds(max_duration, "max_duration")
+        f = np.array(self._frequencies)
+        rows = engine.band_rows(band, f)
+        if len(rows) != 1:
+            raise ValueError("detect() takes one band, (f_lo, f_hi) in Hz, not %d" % len(rows))
+        g, h = engine.band_weights(f, self._wavelet)
+        res = engine.bandpass(result, rows, g, h, (on,))
+        try:
+            c, n = res.n_channels, res.n_cols
+            trace = res.buffer.ptr.value + res._offsets()[on]
+            count, mean, sd = engine.trace_stats(trace, res.pitch, c, n)
+            if units == "sd":
+                with np.errstate(all="ignore"):
+                    hi, lo = (mean + threshold * sd).astype(np.float32), (mean + edge * sd).astype(np.float32)
+            else:
+                hi, lo = np.full(c, hi1, np.float32), np.full(c, lo1, np.float32)
+            bad = np.flatnonzero(~(np.isfinite(hi) & np.isfinite(lo) & (hi >= lo) & (lo >= 0)))
+            if bad.size:
+                raise ValueError("detect(): channel %d: finite hi >= lo >= 0 is required, not hi = %g and lo = %g (the trace's "
+                                 "mean %g, sd %g)" % (bad[0], hi[bad[0]], lo[bad[0]], mean[bad[0]], sd[bad[0]]))
+            runs = engine.trace_runs(trace, res.pitch, c, n, lo)
+        finally:
+            res.free()
+        t = self.time
+        t = None if t is None else np.asarray(t, dtype=np.float64)
+        period = self._stride / float(self._fs)
+        ev = engine.event_filter(runs["trace"], runs["start"], runs["stop"], runs["peak_col"], runs["peak"], hi, t, min_gap,
+                                 min_duration, max_duration, period)
+        when = (lambda col: col * period) if t is None else (lambda col: t[col])
+        events = {"channel": ev["trace"], "start": when(ev["start"]), "stop": when(ev["stop"] - 1), "peak_time": when(ev["peak_col"]),
+                  "peak": ev["peak"], "start_col": ev["start"], "stop_col": ev["stop"], "peak_col": ev["peak_col"]}
+        per_channel = {"mean": mean, "sd": sd, "lo": lo, "hi": hi, "n_columns": count, "n_candidates": runs["counts"]}
+        if squeeze:
+            per_channel = {k: v[0] for k, v in per_channel.items()}
+        first, n_rows = int(rows[0, 0]), int(rows[0, 1])
+        f_lo, f_hi = np.asarray(band, dtype=np.float64).ravel()
+        return _Events(events, per_channel, (float(f_lo), float(f_hi)), (first, n_rows), f[first:first + n_rows], on)
 
     def release_device(self):
         """Frees the device copy of the last result (bringing it over first if nothing has asked for it yet)."""

@@ -292,6 +292,40 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
 int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   const int32_t* bands, int32_t n_bands, const float* g, const float* h,
                   float* d_analytic, float* d_envelope, float* d_power, int64_t out_pitch);
+/* The two steps of threshold-crossing detection on float32 traces that lie on a device (csrc/detect_runs.hip): n_traces
+ * rows of n_cols (1 .. 2^40 - 1) live columns, pitch (>= n_cols) elements apart -- what gcwt_bandpass leaves in
+ * d_envelope / d_power with n_traces = C * n_bands, or any row of an amplitude result.  Both are plan-independent and
+ * know nothing of bands; the device is the one that holds d_trace; arguments are checked before any device call
+ * (GCWT_ERR_INVALID).  Whatever lies between n_cols and pitch may be read and is never used.
+ *
+ * gcwt_trace_stats: per trace, over its columns that are not exactly 0 (the gaps between epochs are exact zeros in
+ * every operator here and must not drag the mean down): n[i] the number of such columns and, with s1 = sum v and s2 =
+ * sum v * v in float64 (the product is exact),
+ *   mean[i] = s1 / n      sd[i] = sqrt(max(s2 / n - mean^2, 0)), the population sd      both 0 where n == 0
+ * n, mean, sd: n_traces entries each in HOST memory.  The sums are made in two steps in a fixed order
+ * (csrc/detect_runs.h spells it out): float64 partial sums of every tile of 1024 columns counted from column 0 go to a
+ * work array -- a lane adds its 4 adjacent columns in ascending order, a butterfly adds the 64 lanes, the 4 waves are
+ * added in ascending order --, then one wave per trace adds the tiles: lane l the tiles l, l + 64, ... in ascending
+ * order, and the same butterfly.  No atomics: a trace gives the same bits alone, among other traces and on a second
+ * call.  For any order |s1 - exact| <= gamma_n sum |v| and |s2 - exact| <= gamma_n sum v^2, gamma_n = n u / (1 - n u),
+ * u = 2^-53.  A NaN or inf column is a column like any other: it is counted and makes mean and sd NaN or inf.  Three
+ * numbers per trace cross to the host.
+ *
+ * gcwt_trace_runs: the maximal runs of columns above a threshold, with their peaks.  lo: n_traces finite thresholds in
+ * HOST memory.  Column t of trace i is above iff v[t] > lo[i] -- strictly, so a NaN is not above --; columns -1 and
+ * n_cols are not above.  A run is a maximal range [start, stop) of above columns; its peak is the largest value in it
+ * and peak_col the smallest column that holds that value.  counts[i] (HOST memory, n_traces entries) is the number of
+ * runs of trace i.  If sum counts <= capacity the records of all runs, ordered by trace and then by ascending start,
+ * are written to the DEVICE arrays d_start, d_stop, d_peak_col (int64) and d_peak (float32) of capacity entries each;
+ * otherwise nothing is written to them and the return is still GCWT_OK: the caller sizes with capacity = 0 (the four
+ * arrays may then be NULL) and calls again.  Everything returned is an integer or an exact copy of an input value, so
+ * the result is defined bit for bit and does not depend on tiling, wave shape or reduction order.  A run that covers
+ * millions of columns has its peak searched by one wave. */
+int gcwt_trace_stats(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
+                     int64_t* n, double* mean, double* sd);
+int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
+                    const float* lo, int64_t capacity,
+                    int64_t* d_start, int64_t* d_stop, int64_t* d_peak_col, float* d_peak, int64_t* counts);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

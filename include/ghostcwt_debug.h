@@ -151,6 +151,11 @@ enum { GCWT_BANDPASS_TILE_COLS = 512, GCWT_BANDPASS_GROUP_BANDS = 4 };
 int gcwt_debug_bandpass_grid(int32_t n_channels, int64_t n_cols, int32_t n_bands, int64_t* n_col_tiles,
                              int32_t* n_band_groups, int64_t* n_blocks);
 
+/* The column tile of gcwt_trace_stats and gcwt_trace_runs: GCWT_RUNS_TILE_COLS columns counted from column 0 (the
+ * last tile of a trace may be ragged); a workgroup takes one (trace, tile).  Nothing returned depends on it for the
+ * runs; for the statistics it is part of the prescribed order of the sums. */
+enum { GCWT_RUNS_TILE_COLS = 1024 };
+
 #ifdef __cplusplus
 }
 #endif
