@@ -1981,7 +1981,12 @@ int gcwt_debug_precision_terms(gcwt_plan* p, float* rounding, float* left_out, f
   HIP_TRY(hipMalloc((void**)&pr.p, sizeof(float) * (size_t)S * Cn));
   PredSegs dbg_segs{};
   dbg_segs.n_channels = p->hp.prm.n_channels;
-  hipError_t he = launch_precision_predict(p->d_bands, p->d_gain, p->d_scale_level, p->d_scale_length, p->ep_dev[p->last_batch].pred_levels, S, L,
+  // the kernel writes the terms of the scales on a decimated level and the energies of levels that have one: the rest
+  // must read as zero, not as whatever the allocation held
+  hipError_t he = hipMemsetAsync(sc.p, 0, sizeof(float) * 2 * (size_t)S * p->last_batch_slots, p->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(lv.p, 0, sizeof(float) * (size_t)L * p->last_batch_slots, p->stream);
+  if (he == hipSuccess)
+    he = launch_precision_predict(p->d_bands, p->d_gain, p->d_scale_level, p->d_scale_length, p->ep_dev[p->last_batch].pred_levels, S, L,
                                            p->last_pt, p->kappa_eps, p->oob_tol, pr.p, lv.p, sc.p, p->last_batch_slots, dbg_segs, p->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(rounding, sc.p, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, p->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(left_out, sc.p + S, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, p->stream);

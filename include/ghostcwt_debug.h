@@ -48,7 +48,8 @@ int gcwt_debug_mean_folded(const gcwt_plan* plan);
  * (S floats each: float32 rounding of the level's stages; what the level's slice of the spectrum leaves out), the
  * energy each level's x_R held (one float per level; may be NULL) and the band energies they come from (384 floats,
  * may be NULL: sum of |X[k]|^2 over the bins 0 < k < P / 2 of band (bits of (float) k >> 19) - 127 * 16, sixteen
- * bands per octave -- summed by the forward row pass, csrc/fwd64.hip: row_band_sums). */
+ * bands per octave -- summed by the forward row pass, csrc/fwd64.hip: row_band_sums).  Scales off the decimated path
+ * and levels without a scale read as zero. */
 int gcwt_debug_precision_terms(gcwt_plan* plan, float* rounding, float* left_out, float* level_energy,
                                float* band_energy);
 /* Block convolution (GCWT_SCALE_BLOCKCONV): the scales in order of kernel length (`order`: n_blockconv entries, at
