@@ -89,6 +89,7 @@ def _load():
                                     C.c_int64]),
         "gcwt_trace_stats": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "gcwt_trace_runs": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, C.c_int64, vp, vp, vp, vp, i64p]),
+        "gcwt_trace_order": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, i64p, C.c_int32, i64p, f32p]),
         "gcwt_plan_create": (C.c_int, [C.POINTER(vp), C.POINTER(Params)]),
         "gcwt_plan_destroy": (None, [vp]),
         "gcwt_plan_get_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),

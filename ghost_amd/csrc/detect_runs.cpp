@@ -16,9 +16,8 @@ static_assert(gcwt::kRunCols == GCWT_RUNS_TILE_COLS, "ghostcwt_debug.h names the
 
 using namespace gcwt;
 
-namespace {
+namespace gcwt {
 
-// everything about the traces that needs no device; fills the grid's numbers
 int check_and_cut(const std::string& op, const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols, TraceArgs* a) {
   if (!d_trace) return fail(GCWT_ERR_INVALID, op + ": d_trace is NULL");
   if (n_traces < 1) return fail(GCWT_ERR_INVALID, op + ": n_traces must be at least 1");
@@ -32,6 +31,10 @@ int check_and_cut(const std::string& op, const float* d_trace, int64_t pitch, in
   a->aligned = pitch % kRunLaneCols == 0 && reinterpret_cast<uintptr_t>(d_trace) % 16 == 0;
   return GCWT_OK;
 }
+
+}  // namespace gcwt
+
+namespace {
 
 int hip_failed(const std::string& op, hipError_t e) { return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e)); }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 
 namespace gcwt {
 
@@ -46,6 +47,31 @@ struct RunArgs {
   int64_t capacity;            // records the four output arrays hold
   long long* start; long long* stop; long long* peak_col; float* peak;
 };
+
+// everything about the traces that needs no device (host; `op` prefixes the message): fills the grid's numbers
+int check_and_cut(const std::string& op, const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols, TraceArgs* a);
+
+struct Cols { float v[kRunLaneCols]; };
+
+// the lane's columns c0 .. c0 + 3 of `row`; 0 for a column at or past n_cols
+__device__ __forceinline__ Cols load_cols(const TraceArgs& a, const float* row, int64_t c0) {
+  Cols c;
+#pragma unroll
+  for (int j = 0; j < kRunLaneCols; ++j) c.v[j] = 0.f;
+  if (c0 >= a.n_cols) return c;
+  if (a.aligned) {                                           // pitch and c0 are multiples of 4: c0 + 3 < pitch
+    const float4 q = *reinterpret_cast<const float4*>(row + c0);
+    c.v[0] = q.x; c.v[1] = q.y; c.v[2] = q.z; c.v[3] = q.w;
+#pragma unroll
+    for (int j = 1; j < kRunLaneCols; ++j)
+      if (c0 + j >= a.n_cols) c.v[j] = 0.f;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kRunLaneCols; ++j)
+      if (c0 + j < a.n_cols) c.v[j] = row[c0 + j];
+  }
+  return c;
+}
 
 hipError_t launch_trace_stats(const TraceArgs& a, TileSums* tiles, TileSums* traces, hipStream_t st);
 // k_run_count, k_run_scan: fills counts, offsets and trace_first

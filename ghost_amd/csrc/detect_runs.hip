@@ -29,28 +29,6 @@ namespace {
 
 constexpr int kWaves = kRunThreads / 64;
 
-struct Cols { float v[kRunLaneCols]; };
-
-// the lane's columns c0 .. c0 + 3 of `row`; 0 for a column at or past n_cols
-__device__ __forceinline__ Cols load_cols(const TraceArgs& a, const float* row, int64_t c0) {
-  Cols c;
-#pragma unroll
-  for (int j = 0; j < kRunLaneCols; ++j) c.v[j] = 0.f;
-  if (c0 >= a.n_cols) return c;
-  if (a.aligned) {                                           // pitch and c0 are multiples of 4: c0 + 3 < pitch
-    const float4 q = *reinterpret_cast<const float4*>(row + c0);
-    c.v[0] = q.x; c.v[1] = q.y; c.v[2] = q.z; c.v[3] = q.w;
-#pragma unroll
-    for (int j = 1; j < kRunLaneCols; ++j)
-      if (c0 + j >= a.n_cols) c.v[j] = 0.f;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kRunLaneCols; ++j)
-      if (c0 + j < a.n_cols) c.v[j] = row[c0 + j];
-  }
-  return c;
-}
-
 // ---- the statistics ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ TileSums wave_add(TileSums s) {
 #pragma unroll

@@ -13,7 +13,7 @@ from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
            "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
-           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "event_filter", "set_option",
+           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "event_filter", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -682,6 +682,63 @@ def trace_runs(buffer_ptr, pitch, n_traces, n_cols, lo):
             buf.free()
     out["counts"] = counts
     return out
+
+
+def trace_order(buffer_ptr, pitch, n_traces, n_cols, ranks, center=None):
+    """Exact order statistics of float32 traces on the device (gcwt_trace_order; include/ghostcwt.h has the definition):
+    per trace, over the columns that are not exactly 0, the value of every 0-based rank of ``ranks`` -- (n_traces, R) or
+    (R,) for all traces, R = 1 .. 4 integers >= 0 -- in the total order of the bit patterns, a radix select on the
+    device.  ``center``: None, or (n_traces,) finite values; the ranks are then those of ``|v - center|`` in float32.
+    -> (n int64 (n_traces,): the columns that count; values float32 (n_traces, R): copies of the keys, bit for bit, and
+    the NaN 0x7fc00000 where the rank is >= n).  8 + 4 R bytes per trace cross to the host."""
+    ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_order")
+    arr = np.asarray(ranks)
+    if arr.ndim == 1:
+        arr = np.broadcast_to(arr, (max(n_traces, 0),) + arr.shape)
+    if (arr.ndim != 2 or arr.shape[0] != n_traces or not 1 <= arr.shape[1] <= 4 or arr.dtype == np.bool_
+            or not np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'ranks' must hold 1 .. 4 integer ranks, (R,) or one row for each of the %d traces, not %s of shape %r"
+                         % (n_traces, arr.dtype, np.shape(ranks)))
+    if arr.size and int(arr.min()) < 0:
+        raise ValueError("'ranks' must be at least 0, not %d" % int(arr.min()))
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    f32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    if center is not None:
+        cen = np.asarray(center)
+        if cen.shape != (n_traces,) or cen.dtype == np.bool_ or not (np.issubdtype(cen.dtype, np.floating) or np.issubdtype(cen.dtype, np.integer)):
+            raise ValueError("'center' must hold one real value for each of the %d traces" % n_traces)
+        with np.errstate(over="ignore"):
+            cen = np.ascontiguousarray(cen, dtype=np.float32)
+        if not np.all(np.isfinite(cen)):
+            raise ValueError("'center' must be finite in float32")
+    n, values = np.zeros(arr.shape[0], np.int64), np.zeros(arr.shape, np.float32)
+    check(lib.gcwt_trace_order(ptr, pitch, n_traces, n_cols, None if center is None else cen.ctypes.data_as(f32p),
+                               arr.ctypes.data_as(i64p), arr.shape[1], n.ctypes.data_as(i64p), values.ctypes.data_as(f32p)))
+    return n, values
+
+
+MAD_TO_SD = 1.482602218505602                       # 1 / Phi^-1(3/4): the sd of a normal distribution from its MAD
+
+
+def trace_median_mad(buffer_ptr, pitch, n_traces, n_cols):
+    """Per-trace median and median absolute deviation of float32 traces on the device, over the columns that are not
+    exactly 0, from exact order statistics (trace_order) and float64 on the host: with the values a, b of the ranks
+    (n - 1) // 2 and n // 2, median = (a + b) / 2, which is exact; then, with center = float32(median) rounded once, the
+    values c, d of the same ranks of |v - center| in float32, mad = (c + d) / 2.  -> (n int64, median float64, mad
+    float64), each (n_traces,); both 0 where n is.  Three calls; a few numbers per trace cross to the host."""
+    n, _ = trace_order(buffer_ptr, pitch, n_traces, n_cols, (0, 0))
+    ranks = np.stack(((n - 1) // 2, n // 2), axis=1)
+    ranks[n == 0] = 0
+    _, mid = trace_order(buffer_ptr, pitch, n_traces, n_cols, ranks)
+    with np.errstate(all="ignore"):
+        median = np.where(n == 0, 0.0, (mid[:, 0].astype(np.float64) + mid[:, 1].astype(np.float64)) / 2)
+        center = np.where(np.isfinite(median), median, 0.0).astype(np.float32)
+    _, dev = trace_order(buffer_ptr, pitch, n_traces, n_cols, ranks, center)
+    with np.errstate(all="ignore"):
+        mad = np.where(n == 0, 0.0, (dev[:, 0].astype(np.float64) + dev[:, 1].astype(np.float64)) / 2)
+    mad = np.where(np.isfinite(median), mad, np.nan)          # a median that is not finite has no deviations
+    mad[n == 0] = 0.0
+    return n, median, mad
 
 
 def event_filter(trace, start, stop, peak_col, peak, hi, time_of_col, min_gap, min_duration, max_duration, period):

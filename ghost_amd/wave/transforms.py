@@ -72,10 +72,35 @@ class _Events:
         self.start_col, self.stop_col, self.peak_col = events["start_col"], events["stop_col"], events["peak_col"]
         self.mean, self.sd, self.lo, self.hi = (per_channel[k] for k in ("mean", "sd", "lo", "hi"))
         self.n_columns, self.n_candidates = per_channel["n_columns"], per_channel["n_candidates"]
+        # stats='median' / baseline=(t0, t1) only; None otherwise
+        self.median, self.mad, self.baseline_cols = (per_channel.get(k) for k in ("median", "mad", "baseline_cols"))
         self.band, self.rows, self.frequencies, self.on = band, rows, frequencies, on
 
     def __len__(self):
         return len(self.channel)
+
+
+def _baseline_columns(baseline, time, n_cols, period):
+    """detect()'s ``baseline=(t0, t1)`` -> the columns [c0, c1) with t0 <= time < t1; ``time``: the columns' times or
+    None (column j at j ``period``).  ValueError for anything but one non-empty stretch."""
+    try:
+        t0, t1 = baseline
+        ok = all(not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) for v in (t0, t1))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (np.isfinite(float(t0)) and np.isfinite(float(t1))):
+        raise ValueError("detect(): 'baseline' must be None or (t0, t1), two finite numbers in seconds, not %r" % (baseline,))
+    t0, t1 = float(t0), float(t1)
+    if not t0 < t1:
+        raise ValueError("detect(): 'baseline' is empty or reversed: t0 = %g is not below t1 = %g" % (t0, t1))
+    t = np.arange(n_cols) * period if time is None else np.asarray(time, dtype=np.float64)[:n_cols]
+    inside = np.flatnonzero((t >= t0) & (t < t1))
+    if inside.size == 0:
+        raise ValueError("detect(): 'baseline' (%g, %g) selects no column of the trace" % (t0, t1))
+    c0, c1 = int(inside[0]), int(inside[-1]) + 1
+    if c1 - c0 != inside.size:
+        raise ValueError("detect(): 'baseline' (%g, %g) selects columns that are not one stretch: the times do not ascend" % (t0, t1))
+    return c0, c1
 
 
 class ContinuousWaveletTransform(WaveletTransform):
@@ -521,7 +546,7 @@ class ContinuousWaveletTransform(WaveletTransform):
                          [f[a:a + n] for a, n in rows], None if t is None else np.asarray(t))
 
     def detect(self, band, *, on="envelope", threshold=3.0, edge=0.0, units="sd", min_duration=0.0, max_duration=None,
-               min_gap=0.0):
+               min_gap=0.0, stats="mean", baseline=None):
         """Threshold-crossing events of one band of the last transform -- ripples, spindles, bursts: the times that
         ``triggered()`` takes --, found on the device.  The transform must have been ``output='complex'`` on one
         device.  ``band``: one (f_lo, f_hi) pair in Hz, its rows and weights those of ``bandpass()``; ``on``:
@@ -545,13 +570,27 @@ class ContinuousWaveletTransform(WaveletTransform):
         single-channel call the per-channel items lose their axis.  ``r.peak_time[r.channel == c]`` is what
         ``triggered()`` takes.  The runs and their peaks are exact, so the events are those of the same definition
         applied to ``bandpass()``'s trace on the host, bit for bit.  The resident result, ``fetch()`` and the result
-        attributes are untouched."""
+        attributes are untouched.
+
+        ``stats='median'``: with ``units='sd'`` the centre is the channel's median and the spread 1.482602218505602 x
+        its median absolute deviation, the sd of a normal distribution with that MAD -- hi = centre + ``threshold``
+        spread, lo = centre + ``edge`` spread, rounded to float32 once -- so the events themselves do not raise the
+        thresholds.  Both are exact order statistics of the trace's non-zero columns, selected on the device
+        (include/ghostcwt.h: gcwt_trace_order; engine.trace_median_mad has the arithmetic), the bits a sort on the host
+        would give, and the per-channel items gain ``median`` and ``mad`` (float64); ``mean`` and ``sd`` are reported
+        as before.  With ``units='absolute'`` it is accepted and changes no threshold.  ``baseline=(t0, t1)``: the
+        statistics of either kind are taken over the columns with t0 <= time < t1 alone -- seconds on the clock of
+        ``time``, or column x K / fs where there are no timestamps -- a quiet stretch; the thresholds hold everywhere
+        and the runs are found over the whole trace.  The columns must be one stretch [c0, c1), reported as
+        ``baseline_cols``; ``n_columns`` then counts the non-zero columns among them."""
         from .. import engine
         result, squeeze = self._resident_rows("detect")
         if not isinstance(on, str) or on not in ("envelope", "power"):
             raise ValueError("detect(): 'on' must be 'envelope' or 'power', not %r" % (on,))
         if not isinstance(units, str) or units not in ("sd", "absolute"):
             raise ValueError("detect(): 'units' must be 'sd' or 'absolute', not %r" % (units,))
+        if not isinstance(stats, str) or stats not in ("mean", "median"):
+            raise ValueError("detect(): 'stats' must be 'mean' or 'median', not %r" % (stats,))
         for name, v in (("threshold", threshold), ("edge", edge)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
                 raise ValueError("detect(): '%s' must be a finite number, not %r" % (name, v))
@@ -572,34 +611,46 @@ class ContinuousWaveletTransform(WaveletTransform):
         if len(rows) != 1:
             raise ValueError("detect() takes one band, (f_lo, f_hi) in Hz, not %d" % len(rows))
         g, h = engine.band_weights(f, self._wavelet)
+        t = self.time
+        t = None if t is None else np.asarray(t, dtype=np.float64)
+        period = self._stride / float(self._fs)
+        c0, c1 = 0, int(result.shape[2])
+        if baseline is not None:
+            c0, c1 = _baseline_columns(baseline, t, c1, period)
         res = engine.bandpass(result, rows, g, h, (on,))
         try:
             c, n = res.n_channels, res.n_cols
             trace = res.buffer.ptr.value + res._offsets()[on]
-            count, mean, sd = engine.trace_stats(trace, res.pitch, c, n)
+            count, mean, sd = engine.trace_stats(trace + 4 * c0, res.pitch, c, c1 - c0)
+            centre, spread = mean, sd
+            if stats == "median":
+                _, median, mad = engine.trace_median_mad(trace + 4 * c0, res.pitch, c, c1 - c0)
+                centre, spread = median, engine.MAD_TO_SD * mad
             if units == "sd":
                 with np.errstate(all="ignore"):
-                    hi, lo = (mean + threshold * sd).astype(np.float32), (mean + edge * sd).astype(np.float32)
+                    hi, lo = (centre + threshold * spread).astype(np.float32), (centre + edge * spread).astype(np.float32)
             else:
                 hi, lo = np.full(c, hi1, np.float32), np.full(c, lo1, np.float32)
             bad = np.flatnonzero(~(np.isfinite(hi) & np.isfinite(lo) & (hi >= lo) & (lo >= 0)))
             if bad.size:
                 raise ValueError("detect(): channel %d: finite hi >= lo >= 0 is required, not hi = %g and lo = %g (the trace's "
-                                 "mean %g, sd %g)" % (bad[0], hi[bad[0]], lo[bad[0]], mean[bad[0]], sd[bad[0]]))
+                                 "%s %g, %s %g)" % (bad[0], hi[bad[0]], lo[bad[0]], "mean" if stats == "mean" else "median",
+                                                    centre[bad[0]], "sd" if stats == "mean" else "1.4826 MAD", spread[bad[0]]))
             runs = engine.trace_runs(trace, res.pitch, c, n, lo)
         finally:
             res.free()
-        t = self.time
-        t = None if t is None else np.asarray(t, dtype=np.float64)
-        period = self._stride / float(self._fs)
         ev = engine.event_filter(runs["trace"], runs["start"], runs["stop"], runs["peak_col"], runs["peak"], hi, t, min_gap,
                                  min_duration, max_duration, period)
         when = (lambda col: col * period) if t is None else (lambda col: t[col])
         events = {"channel": ev["trace"], "start": when(ev["start"]), "stop": when(ev["stop"] - 1), "peak_time": when(ev["peak_col"]),
                   "peak": ev["peak"], "start_col": ev["start"], "stop_col": ev["stop"], "peak_col": ev["peak_col"]}
         per_channel = {"mean": mean, "sd": sd, "lo": lo, "hi": hi, "n_columns": count, "n_candidates": runs["counts"]}
+        if stats == "median":
+            per_channel.update(median=median, mad=mad)
         if squeeze:
             per_channel = {k: v[0] for k, v in per_channel.items()}
+        if baseline is not None:
+            per_channel["baseline_cols"] = (c0, c1)
         first, n_rows = int(rows[0, 0]), int(rows[0, 1])
         f_lo, f_hi = np.asarray(band, dtype=np.float64).ravel()
         return _Events(events, per_channel, (float(f_lo), float(f_hi)), (first, n_rows), f[first:first + n_rows], on)

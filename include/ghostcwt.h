@@ -292,9 +292,9 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
 int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   const int32_t* bands, int32_t n_bands, const float* g, const float* h,
                   float* d_analytic, float* d_envelope, float* d_power, int64_t out_pitch);
-/* The two steps of threshold-crossing detection on float32 traces that lie on a device (csrc/detect_runs.hip): n_traces
+/* The steps of threshold-crossing detection on float32 traces that lie on a device (csrc/detect_runs.hip): n_traces
  * rows of n_cols (1 .. 2^40 - 1) live columns, pitch (>= n_cols) elements apart -- what gcwt_bandpass leaves in
- * d_envelope / d_power with n_traces = C * n_bands, or any row of an amplitude result.  Both are plan-independent and
+ * d_envelope / d_power with n_traces = C * n_bands, or any row of an amplitude result.  All are plan-independent and
  * know nothing of bands; the device is the one that holds d_trace; arguments are checked before any device call
  * (GCWT_ERR_INVALID).  Whatever lies between n_cols and pitch may be read and is never used.
  *
@@ -320,12 +320,38 @@ int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_
  * otherwise nothing is written to them and the return is still GCWT_OK: the caller sizes with capacity = 0 (the four
  * arrays may then be NULL) and calls again.  Everything returned is an integer or an exact copy of an input value, so
  * the result is defined bit for bit and does not depend on tiling, wave shape or reduction order.  A run that covers
- * millions of columns has its peak searched by one wave. */
+ * millions of columns has its peak searched by one wave.
+ *
+ * gcwt_trace_order: exact order statistics of every trace (csrc/trace_order.hip), the bits a sort would give.
+ *   Included columns of trace i: t < n_cols with v[t] != 0 under the IEEE comparison -- both zeros are excluded, a NaN
+ *     is included: gcwt_trace_stats's rule, so the exact zeros of a gap between epochs never count.  n[i] is their
+ *     number.
+ *   Key of an included column: with center == NULL, v[t]; otherwise fabsf(v[t] - center[i]), the difference one float32
+ *     subtraction rounded to nearest even, subnormals kept, contracted with nothing.  Inclusion is decided on v, not on
+ *     the key: a column equal to the centre is included with key +0.
+ *   Order: the unsigned order of ord(k) = bits(k) ^ (bits(k) >> 31 ? 0xffffffff : 0x80000000), which is the numeric
+ *     order wherever that exists and is made total by -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, NaNs ordered by
+ *     payload.
+ *   Output: out[i * n_ranks + j] is the key of rank ranks[i * n_ranks + j] (0-based) among the included columns of
+ *     trace i, copied bit for bit; where the rank is >= n[i] -- also when n[i] == 0 -- the bit pattern 0x7fc00000: the
+ *     caller compares with n.
+ * center (n_traces finite entries, or NULL), ranks (n_traces x n_ranks, each >= 0; n_ranks 1 .. 4), n (n_traces) and out
+ * (n_traces x n_ranks) are HOST memory.  Everything returned is an integer, a copy of an input value or of the one
+ * prescribed subtraction, so the result is defined bit for bit and does not depend on tiling, digit width, wave shape
+ * or the order in which counts are added (integer counts are exact in any order): a trace gives the same bits alone,
+ * among other traces and on a second call.  A radix select from the most significant digit down, 11 / 11 / 10 bits:
+ * per pass one kernel counts digits and one picks each rank's bin; prefixes and remaining ranks stay on the device, six
+ * launches whatever the data, and n_traces x (8 + 4 n_ranks) bytes cross to the host.  NULL pointers, n_ranks outside
+ * 1 .. 4, a negative rank and a centre that is not finite are refused with the index of the first offender. */
 int gcwt_trace_stats(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
                      int64_t* n, double* mean, double* sd);
 int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
                     const float* lo, int64_t capacity,
                     int64_t* d_start, int64_t* d_stop, int64_t* d_peak_col, float* d_peak, int64_t* counts);
+int gcwt_trace_order(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
+                     const float* center,                   /* HOST, n_traces entries, or NULL */
+                     const int64_t* ranks, int32_t n_ranks, /* HOST, n_traces x n_ranks, 0-based; n_ranks 1 .. 4 */
+                     int64_t* n, float* out);               /* HOST: n_traces, n_traces x n_ranks */
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

@@ -157,6 +157,10 @@ int gcwt_debug_bandpass_grid(int32_t n_channels, int64_t n_cols, int32_t n_bands
  * runs; for the statistics it is part of the prescribed order of the sums. */
 enum { GCWT_RUNS_TILE_COLS = 1024 };
 
+/* The chunk of gcwt_trace_order: a workgroup counts GCWT_ORDER_CHUNK_COLS columns of one trace, counted from column 0
+ * (the last chunk of a trace may be ragged), in tiles of GCWT_RUNS_TILE_COLS.  Nothing returned depends on it. */
+enum { GCWT_ORDER_CHUNK_COLS = 8192 };
+
 #ifdef __cplusplus
 }
 #endif
