@@ -18,7 +18,7 @@ const char* const kSelect[] = {"synth16", "synth_cols", "fuse_blocks", "slow_fft
                                "synth_streams", "interp_lgnb", "merge_levels", "split_levels", "interp",
                                "batch_bytes", "stage_floats", "fullband_group", "blockconv",
                                "direct_max_len", "graphs", "plan_threads", "fullband_cache_mb", "auto_threshold_ppb", "auto_kappa_ppb", "auto_oob_ppt", "synth7_order", "host_widen", "host_threads", "fullband4", "cu_count", "synth7_narrow_r", "fold_mean",
-                               "early_interp", "interp_split_r"};
+                               "early_interp", "interp_split_r", "bc_chunk_blocks"};
 // accuracy-changing or measurement hooks: libghostcwt_measure.so only
 const char* const kMeasureOnly[] = {"halo_margin", "interp_q", "interp_taps", "interp_min_r", "prune_inputs", "clock_phases",
                                     "synth_kernel", "synth_drop_stores", "clock_probe", "synthi_pad_kb",

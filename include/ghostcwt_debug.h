@@ -19,7 +19,7 @@ enum {
 /* Named switches read when a plan is created (csrc/options.h): which kernel instantiation or planning
  * layout is used -- "synth16", "synth_cols", "fuse_blocks", "slow_fft", "level_streams", "interp",
  * "interp_grid", "interp_lgnb", "synth_streams", "merge_levels", "split_levels", "early_interp",
- * "interp_split_r" (all compute the same rows; the tests compare them) and the budgets "batch_bytes", "stage_floats".  Options that change
+ * "interp_split_r", "bc_chunk_blocks" (all compute the same rows; the tests compare them) and the budgets "batch_bytes", "stage_floats".  Options that change
  * accuracy or exist for measurements ("halo_margin", "interp_q", "interp_min_r", "prune_inputs",
  * "clock_phases", "synth_kernel", "synth_drop_stores", "clock_probe", "synthi_pad_kb") are refused with
  * GCWT_ERR_UNSUPPORTED by the product library: libghostcwt_measure.so takes them.  clear != 0 returns
