@@ -306,6 +306,25 @@ inline LevelKernel level_kernel(const gcwt_plan* p, const LevelPlan& lp) {
   return lp.fast || (lp.band_shift > 0 && lp.scales.size() <= 256) ? LK_SYNTH7 : LK_SYNTH16;
 }
 
+// The levels' scale lists, one after the other (d_scale_list before k_scale_windows adds the windows): per level the
+// odd kernel lengths (no half-sample delay, real filter) first, even ones after; a Morlet scale's delay is in its
+// complex row (k_gain_rows_complex), so all of them are "plain" and the half-sample ramp is never applied.
+// scale_off[l]: the level's first entry, n_plain[l]: how many of its entries are plain.
+static void level_scale_lists(const HostPlan& hp, std::vector<int32_t>& scale_list, std::vector<int>& scale_off,
+                              std::vector<int>& n_plain) {
+  scale_list.clear();
+  scale_off.assign(hp.levels.size(), 0);
+  n_plain.assign(hp.levels.size(), 0);
+  for (size_t l = 0; l < hp.levels.size(); ++l) {
+    scale_off[l] = (int)scale_list.size();
+    for (int sidx : hp.levels[l].scales)
+      if (hp.morlet || hp.scales[sidx].half_delay == 0.0) scale_list.push_back(sidx);
+    n_plain[l] = (int)scale_list.size() - scale_off[l];
+    for (int sidx : hp.levels[l].scales)
+      if (!hp.morlet && hp.scales[sidx].half_delay != 0.0) scale_list.push_back(sidx);
+  }
+}
+
 // RAII-less span helper: begin/end record events on the stage's stream when profiling
 struct SpanGuard {
   gcwt_plan* p;
@@ -732,15 +751,8 @@ static int gcwt_plan_upload_impl(gcwt_plan* p) {
   std::vector<int> scale_off(hp.levels.size());
   std::vector<int> n_plain(hp.levels.size());
   std::vector<float2> half_tw(hp.levels.size() * 256);
+  level_scale_lists(hp, scale_list, scale_off, n_plain);
   for (size_t l = 0; l < hp.levels.size(); ++l) {
-    scale_off[l] = (int)scale_list.size();
-    // odd kernel lengths (no half-sample delay, real filter) first, even ones after; a Morlet scale's delay is in its
-    // complex row (k_gain_rows_complex), so all of them are "plain" and the half-sample ramp is never applied
-    for (int sidx : hp.levels[l].scales)
-      if (hp.morlet || hp.scales[sidx].half_delay == 0.0) scale_list.push_back(sidx);
-    n_plain[l] = (int)scale_list.size() - scale_off[l];
-    for (int sidx : hp.levels[l].scales)
-      if (!hp.morlet && hp.scales[sidx].half_delay != 0.0) scale_list.push_back(sidx);
     for (int k = 0; k < 256; ++k) {
       const double a = -M_PI * (k - hp.levels[l].band_shift) / (256.0 * hp.levels[l].decimation);
       half_tw[l * 256 + k] = make_float2((float)std::cos(a), (float)std::sin(a));
@@ -2135,6 +2147,31 @@ int gcwt_debug_batch_of(const gcwt_plan* p, int segment, int32_t* first, int32_t
   if (first) *first = f;
   if (count) *count = p->hp.epochs[f].batch_count;
   return GCWT_OK;
+}
+
+int gcwt_debug_scale_lists(gcwt_plan* p, int32_t* level_first, int32_t* level_plain, int32_t* row, int32_t* j_hi,
+                           int32_t max_entries) {
+  if (!p) return set_err(GCWT_ERR_INVALID, "NULL plan");
+  std::vector<int32_t> list;
+  std::vector<int> first, plain;
+  level_scale_lists(p->hp, list, first, plain);
+  const int n = (int)list.size();
+  for (size_t l = 0; l < first.size(); ++l) {
+    if (level_first) level_first[l] = first[l];
+    if (level_plain) level_plain[l] = plain[l];
+  }
+  if (level_first) level_first[first.size()] = n;
+  if (n > max_entries || (!row && !j_hi)) return n;
+  const bool on_device = p->uploaded && p->d_scale_list && p->n_listed == n;
+  if (on_device && n > 0) {                 // the entries as the kernels read them: k_scale_windows has set the top bytes
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipMemcpy(list.data(), p->d_scale_list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < n; ++i) {
+    if (row) row[i] = list[i] & kScaleIndexMask;
+    if (j_hi) j_hi[i] = on_device ? 16 - (int32_t)((uint32_t)list[i] >> 24) : 0;
+  }
+  return n;
 }
 
 int gcwt_debug_exact_gain(const gcwt_plan* p, int scale, const int64_t* a, int64_t b, int64_t n,

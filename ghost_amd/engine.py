@@ -1028,6 +1028,23 @@ class CwtPlan:
                         "nblk": nb.value, "m": m.value, "band_shift": sh.value, "low_cut": cut.value})
         return res
 
+    def debug_scale_lists(self):
+        """Per level (the order of ``debug_levels``): {"rows": the scales in the order the synthesis kernels walk them,
+        "n_plain": how many of them come before the half-sample ramp, "j_hi": first-layer inputs k_synth7 computes per
+        entry (9 .. 16), zeros until the plan's tables are on the device (``upload`` / the first execute)}."""
+        i32p = C.POINTER(C.c_int32)
+        n_lv = lib.gcwt_debug_level_count(self._handle)
+        first, plain = np.zeros(n_lv + 1, np.int32), np.zeros(max(1, n_lv), np.int32)
+        n = lib.gcwt_debug_scale_lists(self._handle, first.ctypes.data_as(i32p), plain.ctypes.data_as(i32p), None, None, 0)
+        if n < 0:
+            check(n)
+        rows, j_hi = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
+        rc = lib.gcwt_debug_scale_lists(self._handle, None, None, rows.ctypes.data_as(i32p), j_hi.ctypes.data_as(i32p), n)
+        if rc < 0:
+            check(rc)
+        return [{"rows": rows[first[l]:first[l + 1]].copy(), "n_plain": int(plain[l]),
+                 "j_hi": j_hi[first[l]:first[l + 1]].copy()} for l in range(n_lv)]
+
     def debug_mean_folded(self):
         """True when the last run summed the channels inside the forward column pass (include/ghostcwt_debug.h)."""
         return bool(lib.gcwt_debug_mean_folded(self._handle))

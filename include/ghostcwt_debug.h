@@ -63,6 +63,15 @@ int gcwt_debug_blockconv_groups(const gcwt_plan* plan, int32_t* first, int32_t* 
 int gcwt_debug_batch_of(const gcwt_plan* plan, int segment, int32_t* first, int32_t* count);
 int gcwt_debug_fetch(gcwt_plan* plan, int what, int channel, int epoch, int level, float* dst,
                      int64_t max_complex);
+/* The lists the synthesis kernels walk, one per level and one after the other: entry i is scale row[i], and for
+ * level l the entries level_first[l] .. level_first[l + 1] - 1 (level_first: n_levels + 1 values), of which the
+ * first level_plain[l] are the kernels of odd length (every scale of a Morlet plan) and the rest carry the level's
+ * half-sample ramp (Synth7Level::n_plain).  j_hi[i]: how many of the sixteen first-layer inputs k_synth7 computes
+ * for the entry (9 .. 16; csrc/kernels.hip: k_scale_windows), read back from the device list's top byte -- 0 as
+ * long as the plan's tables are not on the device (before gcwt_plan_upload or the first execute).  Any pointer may
+ * be NULL.  Returns the number of entries; row and j_hi are filled only when max_entries holds them. */
+int gcwt_debug_scale_lists(gcwt_plan* plan, int32_t* level_first, int32_t* level_plain, int32_t* row,
+                           int32_t* j_hi, int32_t max_entries);
 /* The exact (real) response G of one scale's reference kernel at theta = 2 pi a[i] / b,
  * i < n, evaluated on the HOST by the same code the device bank builder runs
  * (csrc/morse_exact.h).  Needs no GPU. */

@@ -89,6 +89,28 @@ def level_input(X, lvl, B=256):
     return ifft(sl) / (p_big // M)
 
 
+def synth_stage(xr, H, shift, R, lh, hop, lead, ne, B=256):
+    """Steps 3 and 4 of DESIGN.md section 3 on their own, complex128 (ne,): one scale's row of one segment from the
+    level's x_R -- ``level_input``, or what the device holds (``debug_fetch(1, ...)`` over the FFT length) -- and the
+    scale's response H on the level's grid, H[k] at frequency (k - shift) / (B R).  The same quantity as
+    ``cwt_decimated``'s inner loop, evaluated another way: all blocks at once, and the R phases as ONE inverse
+    transform of B R points of the zero-padded block spectrum,
+        y[R m + r] = R IFFT_{B R}(XB_b H)[R m + r]  times  exp(-2 pi i shift (R (b hop - lh) + R m + r) / (B R)),
+    the carrier of a shifted band (block, position and phase in one factor)."""
+    xr = np.asarray(xr, dtype=np.complex128)
+    M, k = xr.size, np.arange(B)
+    nblk = int(math.ceil(math.ceil((lead + ne) / R) / hop))
+    first = np.arange(nblk) * hop - lh
+    XB = fft(xr[(first[:, None] + k[None, :]) % M], axis=1)
+    pad = np.zeros((nblk, B * R), dtype=np.complex128)
+    pad[:, :B] = XB * np.asarray(H)[None, :]
+    z = ifft(pad, axis=1) * R
+    if shift:
+        n = R * first[:, None] + np.arange(B * R)[None, :]
+        z *= np.exp(-2j * np.pi * ((shift * n) % (B * R)) / (B * R))
+    return z[:, R * lh: R * (lh + hop)].reshape(-1)[lead:lead + ne]
+
+
 def level_of_scale(plan):
     """Index into ``plan.debug_levels()`` of every scale (-1: not on a decimated level).  Two levels may share a
     decimation (heavy tails: a second level with a longer halo), so the halo tells them apart."""
