@@ -21,6 +21,7 @@ WAVELET_ENERGY = 0x100
 WAVELET_MORLET = 0x200
 ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_COMM, ERR_COMM_INCOMPLETE = -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
+SMOOTH_MAX_HALF = 4096                              # GCWT_SMOOTH_MAX_HALF
 
 
 class GhostCwtError(RuntimeError):
@@ -90,6 +91,8 @@ def _load():
         "gcwt_trace_stats": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "gcwt_trace_runs": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, C.c_int64, vp, vp, vp, vp, i64p]),
         "gcwt_trace_order": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, i64p, C.c_int32, i64p, f32p]),
+        "gcwt_trace_smooth": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, C.c_int32, i64p, C.c_int64, i32p, C.c_int32, vp,
+                                        C.c_int64]),
         "gcwt_plan_create": (C.c_int, [C.POINTER(vp), C.POINTER(Params)]),
         "gcwt_plan_destroy": (None, [vp]),
         "gcwt_plan_get_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),

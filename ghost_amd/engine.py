@@ -13,7 +13,8 @@ from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
            "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
-           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "event_filter", "set_option",
+           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "smooth_taps", "segments_of",
+           "trace_smooth", "event_filter", "set_option",
            "device_count", "device_name", "device_memory"]
 
 
@@ -739,6 +740,95 @@ def trace_median_mad(buffer_ptr, pitch, n_traces, n_cols):
     mad = np.where(np.isfinite(median), mad, np.nan)          # a median that is not finite has no deviations
     mad[n == 0] = 0.0
     return n, median, mad
+
+
+def smooth_taps(sd_cols):
+    """The centre and one side of a Gaussian window of standard deviation ``sd_cols`` columns, as trace_smooth takes
+    them: half = int(4 sd_cols + 0.5) (scipy.ndimage.gaussian_filter1d's ``truncate=4``), w_k = exp(-k^2 / (2
+    sd_cols^2)) for k = 0 .. half, normalised in float64 so that w_0 + 2 sum w_k = 1 and then rounded to float32 once.
+    -> float32 (half + 1,).  ValueError where half is 0 (the window is narrower than a column) or above
+    _lib.SMOOTH_MAX_HALF (the window counts in columns: an output stride shortens it)."""
+    if isinstance(sd_cols, (bool, np.bool_)) or not isinstance(sd_cols, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(float(sd_cols)) or float(sd_cols) <= 0:
+        raise ValueError("'sd_cols' must be a finite number of columns > 0, not %r" % (sd_cols,))
+    sd = float(sd_cols)
+    half = int(4 * sd + 0.5) if 4 * sd + 0.5 < 2.0 ** 62 else 2 ** 62
+    if half < 1:
+        raise ValueError("a Gaussian of sd %g columns is narrower than a column (4 sd < 0.5): nothing to smooth" % sd)
+    if half > _lib.SMOOTH_MAX_HALF:
+        raise ValueError("a Gaussian of sd %g columns reaches %d columns to either side, above the limit of %d: a larger "
+                         "output_stride shortens it" % (sd, half, _lib.SMOOTH_MAX_HALF))
+    k = np.arange(half + 1, dtype=np.float64)
+    w = np.exp(-k * k / (2 * sd * sd))
+    return (w / (w[0] + 2 * w[1:].sum())).astype(np.float32)
+
+
+def segments_of(time, period, fs, n_cols):
+    """The stretches of columns that belong together on the clock: a boundary lies before column j where ``|time[j] -
+    time[j - 1] - period| > 0.5 / fs`` (trigger_columns' splice rule; ``period``: seconds per column, K / fs).  ``time``:
+    the columns' times, or None: one segment.  -> (n, 2) int64 of (start, stop), ascending and covering [0, n_cols)."""
+    n_cols = int(n_cols)
+    if n_cols < 1:
+        raise ValueError("segments_of() needs at least one column, not %d" % n_cols)
+    if time is None:
+        return np.array([[0, n_cols]], dtype=np.int64)
+    t = np.asarray(time, dtype=np.float64).ravel()
+    if t.size < n_cols:
+        raise ValueError("'time' holds %d columns, fewer than the %d of the trace" % (t.size, n_cols))
+    cut = np.flatnonzero(np.abs(np.diff(t[:n_cols]) - float(period)) > 0.5 / float(fs)) + 1
+    edges = np.concatenate(([0], cut, [n_cols]))
+    return np.ascontiguousarray(np.stack((edges[:-1], edges[1:]), axis=1), dtype=np.int64)
+
+
+def trace_smooth(buffer_ptr, pitch, n_traces, n_cols, taps, segments=None, members=None):
+    """A symmetric FIR along float32 traces on the device -- ``n_traces`` rows of ``n_cols`` live columns, ``pitch``
+    elements apart, at ``buffer_ptr`` (a c_void_p or an address) -- computed there into a new buffer (gcwt_trace_smooth;
+    include/ghostcwt.h has the definition, the order of the float32 operations and the bound of their rounding).
+    ``taps``: w_0 .. w_half as smooth_taps returns them (``[1.0]``: no smoothing).  ``segments``: (n, 2) of (start,
+    stop), ascending and disjoint, as segments_of returns them: a column's window ends where its segment does (zero
+    extension) and a column in no segment is 0; None: one segment.  ``members``: trace indices whose mean, added in
+    the order given, is the one trace that is smoothed; None: every trace on its own.  -> (DeviceBuffer, pitch of its
+    rows, (rows, n_cols)): rows is 1 with ``members``, else n_traces.  The caller frees the buffer; the input is only
+    read and nothing crosses to the host."""
+    ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_smooth")
+    w = np.asarray(taps)
+    if w.ndim != 1 or w.size < 1 or w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+        raise ValueError("'taps' must be a 1-D array of real weights w_0 .. w_half, not %r" % (getattr(w, "shape", None),))
+    with np.errstate(over="ignore"):
+        w = np.ascontiguousarray(w, dtype=np.float32)
+    seg = None
+    if segments is not None:
+        seg = np.asarray(segments)
+        if seg.ndim != 2 or seg.shape[1] != 2 or seg.shape[0] < 1 or seg.dtype == np.bool_ or not np.issubdtype(seg.dtype, np.integer):
+            raise ValueError("'segments' must be an (n, 2) integer array of (start, stop) with n >= 1, not %s of shape %r"
+                             % (seg.dtype, seg.shape))
+        seg = np.ascontiguousarray(seg, dtype=np.int64)
+    mem = None
+    if members is not None:
+        mem = np.asarray(members)
+        if mem.ndim != 1 or mem.size < 1 or mem.dtype == np.bool_ or not np.issubdtype(mem.dtype, np.integer):
+            raise ValueError("'members' must be a 1-D array of at least one trace index, not %s of shape %r" % (mem.dtype, mem.shape))
+        if mem.min() < 0 or mem.max() >= n_traces:
+            raise ValueError("'members' must name traces 0 .. %d, not %d" % (n_traces - 1, mem.min() if mem.min() < 0 else mem.max()))
+        mem = np.ascontiguousarray(mem, dtype=np.int32)
+    n_out, out_pitch = (n_traces if mem is None else 1), _pitch(max(n_cols, 1))
+    args = (ptr, pitch, n_traces, n_cols, w.ctypes.data_as(C.POINTER(C.c_float)), w.size - 1,
+            None if seg is None else seg.ctypes.data_as(C.POINTER(C.c_int64)), 0 if seg is None else len(seg),
+            None if mem is None else mem.ctypes.data_as(C.POINTER(C.c_int32)), 0 if mem is None else mem.size)
+    if n_out < 1 or n_cols < 1:
+        check(lib.gcwt_trace_smooth(*args, None, out_pitch))        # (refused in the library's words)
+    nbytes = n_out * out_pitch * 4
+    free, _ = device_memory()
+    if nbytes > free:
+        raise MemoryError("trace_smooth() needs %d bytes on the device for %d traces of %d columns and %d are free: fewer "
+                          "traces per call" % (nbytes, n_out, n_cols, free))
+    buf = DeviceBuffer(nbytes)
+    try:
+        check(lib.gcwt_trace_smooth(*args, buf.ptr, out_pitch))
+    except Exception:
+        buf.free()
+        raise
+    return buf, out_pitch, (n_out, n_cols)
 
 
 def event_filter(trace, start, stop, peak_col, peak, hi, time_of_col, min_gap, min_duration, max_duration, period):

@@ -67,7 +67,9 @@ class _Bandpass:
 class _Events:
     """What ContinuousWaveletTransform.detect returns (host arrays)."""
 
-    def __init__(self, events, per_channel, band, rows, frequencies, on):
+    def __init__(self, events, per_channel, band, rows, frequencies, on, smooth=None, half=0, combined=False):
+        # smooth: the Gaussian's sd in seconds or None; half: its reach in columns; combined: one trace for all channels
+        self.smooth, self.half, self.combined = smooth, half, combined
         self.channel, self.start, self.stop, self.peak_time, self.peak = (events[k] for k in ("channel", "start", "stop", "peak_time", "peak"))
         self.start_col, self.stop_col, self.peak_col = events["start_col"], events["stop_col"], events["peak_col"]
         self.mean, self.sd, self.lo, self.hi = (per_channel[k] for k in ("mean", "sd", "lo", "hi"))
@@ -546,7 +548,7 @@ class ContinuousWaveletTransform(WaveletTransform):
                          [f[a:a + n] for a, n in rows], None if t is None else np.asarray(t))
 
     def detect(self, band, *, on="envelope", threshold=3.0, edge=0.0, units="sd", min_duration=0.0, max_duration=None,
-               min_gap=0.0, stats="mean", baseline=None):
+               min_gap=0.0, stats="mean", baseline=None, smooth=None, combine=False):
         """Threshold-crossing events of one band of the last transform -- ripples, spindles, bursts: the times that
         ``triggered()`` takes --, found on the device.  The transform must have been ``output='complex'`` on one
         device.  ``band``: one (f_lo, f_hi) pair in Hz, its rows and weights those of ``bandpass()``; ``on``:
@@ -572,6 +574,22 @@ class ContinuousWaveletTransform(WaveletTransform):
         applied to ``bandpass()``'s trace on the host, bit for bit.  The resident result, ``fetch()`` and the result
         attributes are untouched.
 
+        ``smooth``: the standard deviation, in seconds, of a Gaussian that the band trace is smoothed with on the device
+        before anything else looks at it (4 ms is usual for ripples): sd_cols = ``smooth`` fs / K columns, cut at half =
+        int(4 sd_cols + 0.5) columns to either side as scipy.ndimage.gaussian_filter1d cuts it, the weights normalised
+        to sum 1 (engine.smooth_taps; include/ghostcwt.h: gcwt_trace_smooth has the order of the float32 operations).
+        The statistics of either kind, ``baseline`` and the runs are then all taken on the smoothed trace, so ``peak``
+        is its value.  Every epoch -- a stretch of columns one period apart on the clock of ``time``
+        (engine.segments_of) -- is smoothed on its own and continued with zeros past its ends, matching the rows' own
+        'same'-mode edges: the trace reads low within 4 sd of an epoch's ends and nothing leaks from one epoch into
+        the next.  A ``smooth`` narrower than a column (half = 0) or wider than 4096 columns to either side is refused.
+        ``combine=True``: the channels' band traces are averaged on the device, channel 0 first, into one consensus
+        trace (the mean over tetrodes that ripples are usually detected on), which is smoothed if ``smooth`` says so
+        and then takes the place of the channels: one event list, every ``channel`` -1, and the per-channel items lose
+        their axis as after the single-channel call -- after which ``combine`` is refused.  The returned object says
+        what was done in ``smooth`` (seconds or None), ``half`` (columns; 0 without smoothing) and ``combined``.  The
+        defaults launch what the call launched without them.
+
         ``stats='median'``: with ``units='sd'`` the centre is the channel's median and the spread 1.482602218505602 x
         its median absolute deviation, the sd of a normal distribution with that MAD -- hi = centre + ``threshold``
         spread, lo = centre + ``edge`` spread, rounded to float32 once -- so the events themselves do not raise the
@@ -591,6 +609,22 @@ class ContinuousWaveletTransform(WaveletTransform):
             raise ValueError("detect(): 'units' must be 'sd' or 'absolute', not %r" % (units,))
         if not isinstance(stats, str) or stats not in ("mean", "median"):
             raise ValueError("detect(): 'stats' must be 'mean' or 'median', not %r" % (stats,))
+        if not isinstance(combine, (bool, np.bool_)):
+            raise ValueError("detect(): 'combine' must be True or False, not %r" % (combine,))
+        combine = bool(combine)
+        if combine and squeeze:
+            raise ValueError("detect(): 'combine' averages the channels of a multichannel transform: the last one was the "
+                             "single-channel call")
+        taps = None
+        if smooth is not None:
+            if isinstance(smooth, (bool, np.bool_)) or not isinstance(smooth, (int, float, np.integer, np.floating)) \
+                    or not np.isfinite(float(smooth)) or float(smooth) <= 0:
+                raise ValueError("detect(): 'smooth' must be None or a finite number of seconds > 0, not %r" % (smooth,))
+            smooth = float(smooth)
+            try:
+                taps = engine.smooth_taps(smooth * float(self._fs) / self._stride)
+            except ValueError as e:
+                raise ValueError("detect(): 'smooth' = %g s at %g columns per second: %s" % (smooth, float(self._fs) / self._stride, e)) from None
         for name, v in (("threshold", threshold), ("edge", edge)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
                 raise ValueError("detect(): '%s' must be a finite number, not %r" % (name, v))
@@ -615,16 +649,26 @@ class ContinuousWaveletTransform(WaveletTransform):
         t = None if t is None else np.asarray(t, dtype=np.float64)
         period = self._stride / float(self._fs)
         c0, c1 = 0, int(result.shape[2])
+        segments = None
+        if taps is not None or combine:
+            segments = engine.segments_of(t, period, float(self._fs), c1)     # (c1: every column, before the baseline)
         if baseline is not None:
             c0, c1 = _baseline_columns(baseline, t, c1, period)
         res = engine.bandpass(result, rows, g, h, (on,))
+        smoothed = None
         try:
-            c, n = res.n_channels, res.n_cols
+            c, n, pitch = res.n_channels, res.n_cols, res.pitch
             trace = res.buffer.ptr.value + res._offsets()[on]
-            count, mean, sd = engine.trace_stats(trace + 4 * c0, res.pitch, c, c1 - c0)
+            if segments is not None:
+                # the band trace is replaced by its smoothed (and combined) twin and goes at once
+                smoothed, pitch, (c, _) = engine.trace_smooth(trace, pitch, c, n, np.ones(1, np.float32) if taps is None else taps,
+                                                              segments, np.arange(c) if combine else None)
+                res.free()
+                trace = smoothed.ptr.value
+            count, mean, sd = engine.trace_stats(trace + 4 * c0, pitch, c, c1 - c0)
             centre, spread = mean, sd
             if stats == "median":
-                _, median, mad = engine.trace_median_mad(trace + 4 * c0, res.pitch, c, c1 - c0)
+                _, median, mad = engine.trace_median_mad(trace + 4 * c0, pitch, c, c1 - c0)
                 centre, spread = median, engine.MAD_TO_SD * mad
             if units == "sd":
                 with np.errstate(all="ignore"):
@@ -636,24 +680,27 @@ class ContinuousWaveletTransform(WaveletTransform):
                 raise ValueError("detect(): channel %d: finite hi >= lo >= 0 is required, not hi = %g and lo = %g (the trace's "
                                  "%s %g, %s %g)" % (bad[0], hi[bad[0]], lo[bad[0]], "mean" if stats == "mean" else "median",
                                                     centre[bad[0]], "sd" if stats == "mean" else "1.4826 MAD", spread[bad[0]]))
-            runs = engine.trace_runs(trace, res.pitch, c, n, lo)
+            runs = engine.trace_runs(trace, pitch, c, n, lo)
         finally:
             res.free()
+            if smoothed is not None:
+                smoothed.free()
         ev = engine.event_filter(runs["trace"], runs["start"], runs["stop"], runs["peak_col"], runs["peak"], hi, t, min_gap,
                                  min_duration, max_duration, period)
         when = (lambda col: col * period) if t is None else (lambda col: t[col])
-        events = {"channel": ev["trace"], "start": when(ev["start"]), "stop": when(ev["stop"] - 1), "peak_time": when(ev["peak_col"]),
+        events = {"channel": np.full_like(ev["trace"], -1) if combine else ev["trace"], "start": when(ev["start"]), "stop": when(ev["stop"] - 1), "peak_time": when(ev["peak_col"]),
                   "peak": ev["peak"], "start_col": ev["start"], "stop_col": ev["stop"], "peak_col": ev["peak_col"]}
         per_channel = {"mean": mean, "sd": sd, "lo": lo, "hi": hi, "n_columns": count, "n_candidates": runs["counts"]}
         if stats == "median":
             per_channel.update(median=median, mad=mad)
-        if squeeze:
+        if squeeze or combine:
             per_channel = {k: v[0] for k, v in per_channel.items()}
         if baseline is not None:
             per_channel["baseline_cols"] = (c0, c1)
         first, n_rows = int(rows[0, 0]), int(rows[0, 1])
         f_lo, f_hi = np.asarray(band, dtype=np.float64).ravel()
-        return _Events(events, per_channel, (float(f_lo), float(f_hi)), (first, n_rows), f[first:first + n_rows], on)
+        return _Events(events, per_channel, (float(f_lo), float(f_hi)), (first, n_rows), f[first:first + n_rows], on,
+                       smooth=smooth, half=0 if taps is None else len(taps) - 1, combined=combine)
 
     def release_device(self):
         """Frees the device copy of the last result (bringing it over first if nothing has asked for it yet)."""

@@ -342,7 +342,31 @@ int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_
  * among other traces and on a second call.  A radix select from the most significant digit down, 11 / 11 / 10 bits:
  * per pass one kernel counts digits and one picks each rank's bin; prefixes and remaining ranks stay on the device, six
  * launches whatever the data, and n_traces x (8 + 4 n_ranks) bytes cross to the host.  NULL pointers, n_ranks outside
- * 1 .. 4, a negative rank and a centre that is not finite are refused with the index of the first offender. */
+ * 1 .. 4, a negative rank and a centre that is not finite are refused with the index of the first offender.
+ *
+ * gcwt_trace_smooth: a symmetric FIR along every trace, inside segments, optionally after a mean over traces
+ * (csrc/trace_smooth.hip) -- the Gaussian smoothing and the consensus trace of a ripple detector.  Every operation is
+ * one correctly rounded float32 one, contracted with nothing.
+ *   Combine (members given, M = n_members): s = v[m_0], then s = s + v[m_i] in the order of the list (a trace may be
+ *     named twice), then s * (float)(1.0 / M): ONE trace, the input of the next step and the only output row.  Without
+ *     members every trace is smoothed on its own into output row i.
+ *   Smooth: taps w_0 .. w_half are the centre and one side of the window.  Column c of a segment [a, b):
+ *       acc = w_0 * v[c];   acc = fmaf(w_k, v[c - k] + v[c + k], acc) for k = 1 .. half in ascending order
+ *     where a term whose column lies outside [a, b) is an exact 0.f, whatever the trace holds there (a NaN included):
+ *     zero extension at both ends, and a segment never sees its neighbour.  A column in no segment is an exact 0.
+ *     half = 0 with w_0 = 1 copies the segments: the consensus trace without smoothing.
+ *   Reproducibility: a column's bits depend on its own segment's columns and on the taps alone -- not on the tile,
+ *     n_cols, the pitch, the alignment, the other traces or the other segments.  No atomics, no cross-lane sums.
+ *   Rounding: with u = 2^-24 and gamma_m = m u / (1 - m u), |out - exact| <= gamma_(half + 1) sum_k |w_k| (|v[c - k]| +
+ *     |v[c + k]|) (k = 0 once): each product enters at most half + 1 roundings -- the addition of its pair, its own and
+ *     the additions after it; a member mean adds its own M roundings to v before that.
+ * taps (half + 1 finite entries; half 0 .. GCWT_SMOOTH_MAX_HALF -- the window counts in columns, so an output stride
+ * shortens it), segments (n_segments (start, stop) pairs, ascending, disjoint, each holding a column, inside [0,
+ * n_cols); NULL and 0: one segment, every column) and members (n_members trace indices; NULL and 0: none) are HOST
+ * memory.  d_out: 1 row (members) or n_traces rows on the device, out_pitch (>= n_cols) elements apart, not overlapping
+ * d_trace; nothing is written between n_cols and out_pitch.  The tile and its halo are staged in LDS, (1024 + 2 half) x 4
+ * bytes, 36 KB at the limit.  The message of a refusal names the first offending tap, segment or member. */
+enum { GCWT_SMOOTH_MAX_HALF = 4096 };
 int gcwt_trace_stats(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
                      int64_t* n, double* mean, double* sd);
 int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
@@ -352,6 +376,11 @@ int gcwt_trace_order(const float* d_trace, int64_t pitch, int64_t n_traces, int6
                      const float* center,                   /* HOST, n_traces entries, or NULL */
                      const int64_t* ranks, int32_t n_ranks, /* HOST, n_traces x n_ranks, 0-based; n_ranks 1 .. 4 */
                      int64_t* n, float* out);               /* HOST: n_traces, n_traces x n_ranks */
+int gcwt_trace_smooth(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols,
+                      const float* taps, int32_t half,              /* HOST: w_0 .. w_half */
+                      const int64_t* segments, int64_t n_segments,  /* HOST: (start, stop) pairs, or NULL and 0 */
+                      const int32_t* members, int32_t n_members,    /* HOST: traces averaged into ONE output trace, or NULL and 0 */
+                      float* d_out, int64_t out_pitch);
 
 /* Planning: host only, touches no device.  Replaces the per-call setup of
  * transforms.py:179-185 (wavelet lengths, output allocation) and decides, per

@@ -170,6 +170,11 @@ enum { GCWT_RUNS_TILE_COLS = 1024 };
  * (the last chunk of a trace may be ragged), in tiles of GCWT_RUNS_TILE_COLS.  Nothing returned depends on it. */
 enum { GCWT_ORDER_CHUNK_COLS = 8192 };
 
+/* The column tile of gcwt_trace_smooth: GCWT_SMOOTH_TILE_COLS columns counted from column 0 (the last tile of a trace
+ * may be ragged); a workgroup takes one (output trace, tile) and stages it with its halo.  Nothing returned depends on
+ * it. */
+enum { GCWT_SMOOTH_TILE_COLS = 1024 };
+
 #ifdef __cplusplus
 }
 #endif
