@@ -22,6 +22,7 @@ WAVELET_MORLET = 0x200
 ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_COMM, ERR_COMM_INCOMPLETE = -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
 SMOOTH_MAX_HALF = 4096                              # GCWT_SMOOTH_MAX_HALF
+COUPLING_SURROGATES_MAX_WINDOW = 2048               # GCWT_COUPLING_SURROGATES_MAX_WINDOW
 
 
 class GhostCwtError(RuntimeError):
@@ -84,6 +85,8 @@ def _load():
                                      C.c_int64]),
         "gcwt_coupling": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int64, vp, vp, vp, C.c_int64]),
+        "gcwt_coupling_surrogates": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_int64, i64p, C.c_int32, vp, vp, vp, vp, C.c_int64]),
         "gcwt_triggered": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, i64p, C.c_int64,
                                      C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int64]),
         "gcwt_bandpass": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, f32p, vp, vp, vp,
@@ -140,6 +143,7 @@ def _load():
         "gcwt_debug_bandwidth": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_double)]),
         "gcwt_debug_coherence_tasks": (C.c_int, [C.c_int32, i32p, C.c_int32, i32p, i32p, i32p, i32p, i32p, C.c_int32]),
         "gcwt_debug_coupling_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, i32p, i64p, i64p, i64p]),
+        "gcwt_debug_coupling_surrogates_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, i32p, i64p, i64p]),
         "gcwt_debug_triggered_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, i32p, i64p, i64p]),
         "gcwt_debug_bandpass_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, i64p, i32p, i64p]),
         "gcwt_debug_fetch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int64]),

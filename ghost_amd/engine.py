@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
-           "coupling", "coupling_rows", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
+           "coupling", "coupling_rows", "CouplingSurrogatesResult", "coupling_surrogates", "surrogate_shifts", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
            "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "smooth_taps", "segments_of",
            "trace_smooth", "event_filter", "set_option",
            "device_count", "device_name", "device_memory"]
@@ -366,6 +366,76 @@ def coupling(result, phase_rows, amp_rows, window):
         lambda ptr: check(lib.gcwt_coupling(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1],
                                             amp_rows[0], amp_rows[1], window, ptr["vector"], ptr["mvl"], ptr["amplitude"],
                                             res.pitch)))
+
+
+def surrogate_shifts(k, window, min_cols, seed):
+    """The shift list of a coupling_surrogates() call: ``np.random.default_rng(seed).integers(min_cols, window - min_cols
+    + 1, size=k)`` as int64 -- ``k`` shifts in columns, each at least ``min_cols`` away from 0 and from ``window`` (a
+    shift below about one period of the phase rhythm leaves the coupling in place).  ValueError unless ``k`` is an int
+    in 2 .. 4096, ``min_cols`` an int >= 1 and ``window >= 2 min_cols + 1``."""
+    window = bin_window(window)
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 4096:
+        raise ValueError("the number of surrogates must be an integer in 2 .. 4096, not %r" % (k,))
+    if isinstance(min_cols, (bool, np.bool_)) or not isinstance(min_cols, (int, np.integer)) or int(min_cols) < 1:
+        raise ValueError("the smallest shift must be an integer number of columns >= 1, not %r" % (min_cols,))
+    if window < 2 * int(min_cols) + 1:
+        raise ValueError("window = %d columns leaves no shift at least %d columns away from both ends of a bin: it must "
+                         "be at least 2 x %d + 1" % (window, int(min_cols), int(min_cols)))
+    return np.random.default_rng(seed).integers(int(min_cols), window - int(min_cols) + 1, size=int(k)).astype(np.int64)
+
+
+class CouplingSurrogatesResult(_RowOpResult):
+    """What coupling_surrogates() left on the device: ``mean`` and ``sd`` (C, P, A, B) float32, ``count_ge`` (C, P, A, B)
+    int32 and, when kept, ``surrogates`` (K, C, P, A, B) float32 in one DeviceBuffer, rows ``pitch`` elements apart;
+    ``shifts`` (K,) int64; ``phase_rows`` and ``amp_rows``: (first, count); ``window``; ``counts`` (B,): the columns of
+    each bin.  ``to_host()`` brings the planes over."""
+
+    def __init__(self, buffer, n_channels, phase_rows, amp_rows, n_bins, pitch, window, counts, shifts, keep):
+        self.buffer, self.pitch, self.window, self.counts = buffer, int(pitch), int(window), counts
+        self.phase_rows, self.amp_rows, self.shifts, self.keep = tuple(phase_rows), tuple(amp_rows), shifts, bool(keep)
+        self.n_channels, self.n_phase, self.n_amp, self.n_bins = int(n_channels), int(phase_rows[1]), int(amp_rows[1]), int(n_bins)
+
+    def _planes(self):
+        lead = (self.n_channels, self.n_phase, self.n_amp)
+        planes = (("mean", np.float32, lead), ("sd", np.float32, lead), ("count_ge", np.int32, lead))
+        if self.keep:
+            planes += (("surrogates", np.float32, (len(self.shifts),) + lead),)
+        return planes, self.n_bins
+
+
+def coupling_surrogates(result, phase_rows, amp_rows, window, shifts, keep=False):
+    """Shift-surrogate statistics of coupling()'s mvl, computed where the result lies (gcwt_coupling_surrogates;
+    include/ghostcwt.h has the definition): for every shift of ``shifts`` (1-D integers, 2 .. 4096 of them, each in [0,
+    window) columns; surrogate_shifts() draws such a list) the amplitude row is moved circularly inside each bin and the
+    mvl made again.  ``window`` is at most _lib.COUPLING_SURROGATES_MAX_WINDOW columns.  ``keep``: every surrogate mvl
+    stays too.  The result itself is only read.  -> CouplingSurrogatesResult."""
+    window = bin_window(window)
+    c, s, n = _resident_complex(result, "coupling_surrogates", "a result sharded over several GPUs is not supported")
+    phase_rows = _row_range(phase_rows, s, "phase_rows")
+    amp_rows = _row_range(amp_rows, s, "amp_rows")
+    if window > _lib.COUPLING_SURROGATES_MAX_WINDOW:
+        raise ValueError("window = %d columns is above the largest the surrogates can take, %d (a bin is held in the LDS of "
+                         "one compute unit): a shorter window or an output_stride" % (window, _lib.COUPLING_SURROGATES_MAX_WINDOW))
+    arr = np.asarray(shifts)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer) or arr.ndim != 1:
+        raise ValueError("shifts must be a 1-D array of integer shifts in columns, not %s of shape %r" % (arr.dtype, arr.shape))
+    if not 2 <= arr.size <= 4096:
+        raise ValueError("shifts must hold 2 .. 4096 shifts, not %d" % arr.size)
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    bad = np.flatnonzero((arr < 0) | (arr >= window))
+    if bad.size:
+        raise ValueError("shifts[%d] = %d is outside [0, window = %d)" % (bad[0], arr[bad[0]], window))
+    n_bins = -(-n // window)
+    res = CouplingSurrogatesResult(None, c, phase_rows, amp_rows, n_bins, _pitch(n_bins), window,
+                                   _bin_counts(n, window, n_bins), arr, keep)
+    return _run_into(
+        res, "coupling_surrogates", "%d channels, %d x %d rows, %d bins%s"
+        % (c, phase_rows[1], amp_rows[1], n_bins, ", %d surrogates kept" % arr.size if keep else ""),
+        "narrower bands, a wider window or keep=False",
+        lambda ptr: check(lib.gcwt_coupling_surrogates(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1],
+                                                       amp_rows[0], amp_rows[1], window,
+                                                       arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, ptr["mean"],
+                                                       ptr["sd"], ptr["count_ge"], ptr.get("surrogates"), res.pitch)))
 
 
 def _seconds(value, what):

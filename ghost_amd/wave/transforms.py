@@ -42,10 +42,13 @@ class _Coherence:
 class _Coupling:
     """What ContinuousWaveletTransform.coupling returns (host arrays)."""
 
-    def __init__(self, mvl, vector, amplitude, phase_frequencies, amplitude_frequencies, time, window):
+    def __init__(self, mvl, vector, amplitude, phase_frequencies, amplitude_frequencies, time, window, stats=None):
         self.mvl, self.vector, self.amplitude = mvl, vector, amplitude
         self.phase_frequencies, self.amplitude_frequencies = phase_frequencies, amplitude_frequencies
         self.time, self.window = time, window
+        # surrogates=K only; None otherwise
+        self.surrogate_mean, self.surrogate_sd, self.z, self.p, self.shifts, self.surrogates = (
+            (stats or {}).get(k) for k in ("mean", "sd", "z", "p", "shifts", "surrogates"))
 
 
 class _Triggered:
@@ -433,7 +436,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         return _Coherence(out["coherence"], out["cross"], out["power"], pairs.astype(np.int64),
                           np.array(self._frequencies), None if t is None else np.asarray(t)[::window], window)
 
-    def coupling(self, *, phase, amplitude, window):
+    def coupling(self, *, phase, amplitude, window, surrogates=None, min_shift=None, seed=0, keep_surrogates=False):
         """Phase-amplitude coupling inside each channel of the last transform -- does the amplitude of a fast band ride
         on the phase of a slow one? --, reduced on the device over bins of ``window`` columns (an integer >= 2; with
         an output stride K a column is K samples).  The transform must have been ``output='complex'`` on one device.
@@ -447,25 +450,68 @@ class ContinuousWaveletTransform(WaveletTransform):
         the channel axis is dropped.  Bins are plain column ranges, B = ceil(columns / window), the last one may be
         short; a bin inside a gap between epochs is exactly 0 in all three.  A bin shorter than about one period of
         the phase row reads high whatever the signal -- a property of the estimator (one effective sample), not an
-        error: choose ``window`` as several periods of the lowest phase frequency.  No surrogate statistics are made.
-        Only the reduced arrays cross to the host; the resident result, ``fetch()`` and the result attributes are
-        untouched."""
+        error: choose ``window`` as several periods of the lowest phase frequency.  A raw mvl is therefore read against
+        its shift surrogates (Canolty et al. 2006): ``surrogates=K`` (an int in 2 .. 4096; ``window`` at most
+        2048 columns then, GCWT_COUPLING_SURROGATES_MAX_WINDOW; C: gcwt_coupling_surrogates) draws K shifts with
+        ``engine.surrogate_shifts(K, window, min_cols, seed)`` -- one list for every channel, cell and bin; ``min_shift`` in
+        seconds, default one period of the lowest selected phase frequency, becomes ``min_cols = ceil(min_shift fs /
+        stride)`` columns --, and for each shift L moves the amplitude row circularly inside each bin, |W[a]| at column b
+        + (r + L mod cnt) mod cnt against u at b + r, and makes the mvl again on the device, in coupling()'s arithmetic
+        and order.  The object then also has ``surrogate_mean`` and ``surrogate_sd`` (C, P, A, B) float32 (sums in
+        float64, the sd with K - 1), ``z`` = (mvl - mean) / sd (float64 on the host, 0 where sd == 0, float32), ``p`` =
+        (1 + the number of surrogates >= mvl) / (K + 1) float32, ``shifts`` (K,) int64 and, with ``keep_surrogates``,
+        ``surrogates`` (K, C, P, A, B) float32, whose plane of a shift 0 has the bits of ``mvl``; without ``surrogates``
+        these are None and the call is what it was.  The shift is bin-local and circular: it keeps the non-stationarity
+        of the recording out of the null, never reads across a gap and leaves S fixed.  The price: the surrogates
+        decorrelate only if a bin spans several coherence times of the phase rhythm -- a perfectly periodic rhythm gives z
+        near 0 however strong its coupling --, a bin partly inside a gap has surrogates biased low, and a bin wholly
+        inside a gap is 0 everywhere with p = 1 and z = 0.  Only the reduced arrays cross to the host; the resident
+        result, ``fetch()`` and the result attributes are untouched."""
         from .. import engine
         window = engine.bin_window(window)
         result, squeeze = self._resident_rows("coupling")
         f = np.array(self._frequencies)
         phase_rows = engine.coupling_rows(phase, f, "phase")
         amp_rows = engine.coupling_rows(amplitude, f, "amplitude")
+        f_phase = f[phase_rows[0]:phase_rows[0] + phase_rows[1]]
+        shifts = None
+        if surrogates is not None:
+            if window > engine._lib.COUPLING_SURROGATES_MAX_WINDOW:
+                raise ValueError("coupling(): with surrogates, window = %d columns is above the largest bin the device "
+                                 "holds, %d columns (GCWT_COUPLING_SURROGATES_MAX_WINDOW): a shorter window or an "
+                                 "output_stride" % (window, engine._lib.COUPLING_SURROGATES_MAX_WINDOW))
+            per_col = float(self._stride) / float(self._fs)      # seconds per column
+            if min_shift is None:
+                min_cols = int(np.ceil(float(self._fs) / (self._stride * float(f_phase.min()))))
+            else:
+                if isinstance(min_shift, (bool, np.bool_)) or not isinstance(min_shift, (int, float, np.integer, np.floating)) \
+                        or not np.isfinite(float(min_shift)) or float(min_shift) <= 0:
+                    raise ValueError("coupling(): 'min_shift' must be a finite number of seconds > 0, not %r" % (min_shift,))
+                min_cols = max(1, int(np.ceil(float(min_shift) / per_col)))
+            shifts = engine.surrogate_shifts(surrogates, window, min_cols, seed)
         res = engine.coupling(result, phase_rows, amp_rows, window)
         try:
             out = res.to_host()
         finally:
             res.free()
+        stats = None
+        if shifts is not None:
+            res = engine.coupling_surrogates(result, phase_rows, amp_rows, window, shifts, keep=keep_surrogates)
+            try:
+                stats = res.to_host()
+            finally:
+                res.free()
+            mean, sd = stats["mean"].astype(np.float64), stats["sd"].astype(np.float64)
+            stats["z"] = np.where(sd > 0, (out["mvl"].astype(np.float64) - mean) / np.where(sd > 0, sd, 1.0), 0.0).astype(np.float32)
+            stats["p"] = ((1.0 + stats.pop("count_ge")) / (shifts.size + 1.0)).astype(np.float32)
+            stats["shifts"] = shifts
         if squeeze:
             out = {k: v[0] for k, v in out.items()}
+            if stats is not None:
+                stats = {k: v if k == "shifts" else v[:, 0] if k == "surrogates" else v[0] for k, v in stats.items()}
         t = self.time
-        return _Coupling(out["mvl"], out["vector"], out["amplitude"], f[phase_rows[0]:phase_rows[0] + phase_rows[1]],
-                         f[amp_rows[0]:amp_rows[0] + amp_rows[1]], None if t is None else np.asarray(t)[::window], window)
+        return _Coupling(out["mvl"], out["vector"], out["amplitude"], f_phase, f[amp_rows[0]:amp_rows[0] + amp_rows[1]],
+                         None if t is None else np.asarray(t)[::window], window, stats)
 
     def triggered(self, events, *, before, after, freq_limits=None):
         """Event-locked time-frequency averages of the last transform -- the peri-event spectrogram, the evoked

@@ -236,12 +236,40 @@ int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32
  * 0 in all three.  The sums are float32 in gcwt_coherence's fixed order and the normalisation is a prescribed sequence
  * of correctly rounded operations (coupling.hip), neither depending on which other rows are asked for: a cell (p, a)
  * gives the same bits alone and inside any larger ranges.  A bin shorter than about one period of the phase row reads
- * high whatever the signal (one effective sample): a property of the estimator; no surrogate statistics are made.
- * Plan-independent; the device is the one that holds d_rows.  Arguments are checked before any device call
- * (GCWT_ERR_INVALID). */
+ * high whatever the signal (one effective sample): a property of the estimator, and the reason a raw mvl is read
+ * against its shift surrogates (gcwt_coupling_surrogates below).  Plan-independent; the device is the one that holds
+ * d_rows.  Arguments are checked before any device call (GCWT_ERR_INVALID). */
 int gcwt_coupling(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   int32_t phase_first, int32_t n_phase, int32_t amp_first, int32_t n_amp, int64_t window,
                   float* d_vector, float* d_mvl, float* d_amplitude, int64_t out_pitch);
+/* Shift-surrogate statistics of gcwt_coupling's mvl, on the device that holds the rows (csrc/coupling_surrogates.hip).
+ * d_rows ... window, the bins, u_p, |W[c][a]|, M, S and cnt_m are exactly those of gcwt_coupling, with window <=
+ * GCWT_COUPLING_SURROGATES_MAX_WINDOW (a bin is held in the LDS of one compute unit).  shifts: n_shifts = K (2 .. 4096)
+ * shifts in columns, each in [0, window), in HOST memory; one list serves every channel, cell and bin.  For a shift L
+ * the surrogate of a bin with first column b moves the amplitude row circularly inside the bin:
+ *   M_L = sum_{r = 0}^{cnt_m - 1} |W[c][a][b + (r + L') mod cnt_m]| u_p(b + r),   L' = L mod cnt_m
+ *   mvl_L = min(|M_L| / S, 1), exactly 0 where S == 0   (S does not change under the shift)
+ * (L' differs from L only in the short last bin.)  With T = sum_k mvl_k and Q = sum_k mvl_k^2 over the list, accumulated
+ * in float64 in a fixed order that depends on K alone (coupling_surrogates.hip), each result rounded to float32 once:
+ *   d_mean [C][P][A][B]           float32  T / K
+ *   d_sd [C][P][A][B]             float32  sqrt(max(0, (Q - T^2 / K) / (K - 1)))
+ *   d_count_ge [C][P][A][B]       int32    the number of k with mvl_k >= mvl_0 as float32, mvl_0 the L = 0 value: the
+ *                                          p-value of the observed mvl is (1 + count_ge) / (K + 1)
+ *   d_surrogates [K][C][P][A][B]  float32  every mvl_k, or NULL
+ * Any may be NULL, but not all; their rows are out_pitch (>= B) elements apart.  The arithmetic of a term and the order
+ * of every float32 sum are gcwt_coupling's: mvl_L at L = 0 has the bits of its d_mvl, a cell (p, a) gives the same bits
+ * alone and inside any larger ranges, and two runs give the same bits.  The shift is bin-local and circular: it keeps
+ * the non-stationarity of the recording out of the null, never reads across an epoch gap and leaves S fixed.  The price:
+ * the surrogates decorrelate only if the bin spans several coherence times of the phase rhythm -- a perfectly periodic
+ * rhythm gives z near 0 however strong its coupling; a bin partly inside a gap has surrogates biased low; a bin wholly
+ * inside a gap is 0 in every output but count_ge = K (p = 1, z = 0).  Plan-independent; the device is the one that
+ * holds d_rows.  Arguments -- every shift among them -- are checked before any device call (GCWT_ERR_INVALID); a device
+ * that does not grant the kernel its LDS is GCWT_ERR_HIP. */
+enum { GCWT_COUPLING_SURROGATES_MAX_WINDOW = 2048 };
+int gcwt_coupling_surrogates(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                             int32_t phase_first, int32_t n_phase, int32_t amp_first, int32_t n_amp, int64_t window,
+                             const int64_t* shifts, int32_t n_shifts, float* d_mean, float* d_sd, int32_t* d_count_ge,
+                             float* d_surrogates, int64_t out_pitch);
 /* Event-locked averages of the rows of a device-resident complex result, on the device that holds it
  * (csrc/triggered.hip).  d_rows, pitch and n_cols are those of gcwt_coherence; the rows are [row_first, row_first +
  * n_rows) inside [0, n_scales).  events: n_events (1 .. 2^24 = E) event columns in HOST memory, in any order, repeats

@@ -140,6 +140,17 @@ int gcwt_debug_coupling_grid(int32_t n_channels, int64_t n_cols, int32_t n_phase
                              int32_t* n_phase_tiles, int32_t* n_amp_tiles, int64_t* run_bins, int64_t* n_runs,
                              int64_t* n_blocks);
 
+/* Host only: the grid gcwt_coupling_surrogates launches.  The tiles are formed as gcwt_coupling's, of
+ * GCWT_COUPLING_SURROGATES_TILE_PHASE x GCWT_COUPLING_SURROGATES_TILE_AMP rows; a workgroup of
+ * GCWT_COUPLING_SURROGATES_WAVES waves takes one (channel, bin, phase tile, amplitude tile) and every shift.  n_blocks
+ * counts the workgroups: every tile of every (channel, bin), the (channel, bin)s padded to a multiple of 8 so that the
+ * tiles of one of them lie 8 workgroups apart.  lds_bytes: the LDS a workgroup asks for at this window (64 bytes per
+ * column, the planes padded to 4 columns, plus the waves' sums).  Any pointer may be NULL.  Returns GCWT_OK or an error
+ * code < 0 (a window above GCWT_COUPLING_SURROGATES_MAX_WINDOW and a grid of more than 2^31 - 1 workgroups among them). */
+enum { GCWT_COUPLING_SURROGATES_TILE_PHASE = 4, GCWT_COUPLING_SURROGATES_TILE_AMP = 8, GCWT_COUPLING_SURROGATES_WAVES = 8 };
+int gcwt_debug_coupling_surrogates_grid(int32_t n_channels, int64_t n_cols, int32_t n_phase, int32_t n_amp, int64_t window,
+                                        int32_t* n_phase_tiles, int32_t* n_amp_tiles, int64_t* n_blocks, int64_t* lds_bytes);
+
 /* Host only: the grid gcwt_triggered launches for n_rows rows and before + after + 1 lags.  The rows form tiles of
  * GCWT_TRIGGERED_TILE_ROWS, counted from the first row asked for, and the lags tiles of GCWT_TRIGGERED_TILE_LAGS,
  * counted from lag 0 (the last tile of either may be ragged); a workgroup takes one (channel, lag tile, row tile) and
