@@ -91,6 +91,8 @@ def _load():
                                      C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int64]),
         "gcwt_bandpass": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, f32p, vp, vp, vp,
                                     C.c_int64]),
+        "gcwt_ridge": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, f32p, C.c_float, i64p,
+                                 C.c_int64, vp, vp, vp, vp, C.c_int64]),
         "gcwt_trace_stats": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "gcwt_trace_runs": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, C.c_int64, vp, vp, vp, vp, i64p]),
         "gcwt_trace_order": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, i64p, C.c_int32, i64p, f32p]),

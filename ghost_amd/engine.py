@@ -13,7 +13,7 @@ from ._lib import lib, check
 
 __all__ = ["CwtPlan", "DeviceBuffer", "DeviceResult", "CoherenceResult", "coherence", "coherence_pairs", "CouplingResult",
            "coupling", "coupling_rows", "CouplingSurrogatesResult", "coupling_surrogates", "surrogate_shifts", "TriggeredResult", "triggered", "trigger_columns", "BandpassResult",
-           "bandpass", "band_rows", "band_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "smooth_taps", "segments_of",
+           "bandpass", "band_rows", "band_weights", "RidgeResult", "ridge", "ridge_weights", "trace_stats", "trace_runs", "trace_order", "trace_median_mad", "smooth_taps", "segments_of",
            "trace_smooth", "event_filter", "set_option",
            "device_count", "device_name", "device_memory"]
 
@@ -679,6 +679,129 @@ def bandpass(result, rows, g, h, outputs=("analytic", "envelope", "power")):
                                             len(arr), None if g is None else g.ctypes.data_as(f32p),
                                             None if h is None else h.ctypes.data_as(f32p), ptr.get("analytic"),
                                             ptr.get("envelope"), ptr.get("power"), res.pitch)))
+
+
+def ridge_weights(frequencies, wavelet):
+    """The weights e of ridge() for the rows at ``frequencies`` (Hz) of a transform with ``wavelet`` (Morse or Morlet,
+    its ``fs`` set for Morlet): float32, S entries, computed in float64 and cast once.  Host only.  e_r is the square of
+    the amplitude gain that makes a sinusoid of amplitude A at f_r read sqrt(e_r |w_r|^2) = A on its own row:
+      Morse, whose response peaks at 2 on every row: a row reads A as it is, e_r = 1;
+      Morlet(w0), energy-normalised, sigma_r = (w0 + sqrt(2 + w0^2)) fs / (4 pi f_r) samples: the row reads
+        sqrt(sigma_r) peak A,  peak = pi^-1/4 sqrt(pi / 2) psi(v_r),  v_r = (w0 + sqrt(2 + w0^2)) / 2 and psi as in
+        _morlet_constants;  e_r = 1 / (sigma_r peak^2).  Without it the ridge of an energy-normalised transform leans
+        to low frequencies."""
+    from .wave import morlet, morse
+    f = np.asarray(frequencies, dtype=np.float64).ravel()
+    if f.size < 1:
+        raise ValueError("ridge_weights() needs at least 1 frequency, not %d" % f.size)
+    if not np.all(np.isfinite(f)) or np.any(f <= 0):
+        raise ValueError("the frequencies must be finite and positive")
+    if isinstance(wavelet, morlet.Morlet):
+        w0 = float(wavelet.w0)
+        v = (w0 + np.sqrt(2 + w0 ** 2)) / 2
+        sigma = v * float(wavelet.fs) / (2 * np.pi * f)
+        psi = np.exp(-0.5 * (v - w0) ** 2) - np.exp(-0.5 * w0 ** 2 - 0.5 * v ** 2)
+        peak = np.pi ** -0.25 * np.sqrt(np.pi / 2) * psi
+        e = 1.0 / (sigma * peak ** 2)
+    elif isinstance(wavelet, morse.Morse):
+        e = np.ones_like(f)
+    else:
+        raise ValueError("ridge_weights() knows Morse and Morlet wavelets, not %r" % (wavelet,))
+    return e.astype(np.float32)
+
+
+_RIDGE_OUTPUTS = (("row", np.int32), ("amplitude", np.float32), ("offset", np.float32), ("frequency", np.float32))
+
+
+class RidgeResult(_RowOpResult):
+    """What ridge() left on the device, each (C, B, N) with rows ``pitch`` elements apart in one DeviceBuffer and only
+    those of ``outputs``: ``row`` int32, ``amplitude``, ``offset`` and ``frequency`` float32; ``rows``: (B, 2) of (first,
+    count).  ``to_host()`` brings them over; until ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr
+    + _offsets()[name]``."""
+
+    def __init__(self, buffer, n_channels, rows, n_cols, pitch, outputs):
+        self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), rows, tuple(outputs)
+        self.n_channels, self.n_bands, self.n_cols = int(n_channels), len(rows), int(n_cols)
+
+    def _planes(self):
+        lead = (self.n_channels, self.n_bands)
+        return tuple((name, dtype, lead) for name, dtype in _RIDGE_OUTPUTS if name in self.outputs), self.n_cols
+
+
+def _ridge_outputs(outputs):
+    names = [name for name, _ in _RIDGE_OUTPUTS]
+    seq = (outputs,) if isinstance(outputs, str) else outputs
+    try:
+        ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("'outputs' must name at least one of %s, each once, not %r" % (", ".join(names), outputs))
+    return tuple(seq)
+
+
+def _ridge_table(w, n_scales, what, strict):
+    arr = np.asarray(w)
+    if arr.shape != (n_scales,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'%s' must hold one real number for each of the result's %d rows" % (what, n_scales))
+    with np.errstate(over="ignore"):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if not np.all(np.isfinite(arr)) or np.any(arr <= 0 if strict else arr < 0):
+        raise ValueError("'%s' must be finite and %s" % (what, "above 0" if strict else "at least 0"))
+    return arr
+
+
+def _ridge_segments(segments, n_cols):
+    seg = np.asarray(segments)
+    if seg.ndim != 2 or seg.shape[1] != 2 or seg.shape[0] < 1 or seg.dtype == np.bool_ or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError("'segments' must be an (n, 2) integer array of (start, stop) with n >= 1, not %s of shape %r"
+                         % (seg.dtype, seg.shape))
+    seg = np.ascontiguousarray(seg, dtype=np.int64)
+    end = 0
+    for k, (start, stop) in enumerate(seg):
+        if stop <= start or start != end or stop > n_cols:
+            raise ValueError("segments[%d] = [%d, %d): the segments must ascend, each hold a column and start where the one "
+                             "before stops (here %d), from 0 to the result's %d columns" % (k, start, stop, end, n_cols))
+        end = int(stop)
+    if end != n_cols:
+        raise ValueError("segments[%d] stops at %d: the segments must cover the result's %d columns" % (len(seg) - 1, end, n_cols))
+    return seg
+
+
+def ridge(result, rows, e, nu, hz_per_cycle, segments, outputs=("row", "amplitude", "frequency", "offset")):
+    """The spectral ridge of bands of a complex DeviceResult and the instantaneous frequency on it, computed where the
+    result lies (gcwt_ridge; include/ghostcwt.h has the definition): for every band of ``rows`` -- (B, 2) of (first,
+    count) as band_rows returns them; bands may overlap -- and every column the ``row`` of largest e_r |w_r|^2 (-1 in a
+    gap), its ``amplitude`` sqrt(e_r |w_r|^2), the parabolic sub-row ``offset`` and the ``frequency`` in Hz from the
+    phase advance on that row between the neighbouring columns of the same segment.  ``e``: (S,) weights > 0 as
+    ridge_weights returns them; ``nu``: (S,) >= 0, the phase advance each row expects per column, 2 pi f_r K / fs;
+    ``hz_per_cycle``: fs / K; ``segments``: (n, 2) of (start, stop) as segments_of returns them, covering every column.
+    Only the planes of ``outputs`` are allocated.  The result itself is only read.  -> RidgeResult, which stays on the
+    device until ``to_host()`` / ``free()``."""
+    c, s, n = _resident_complex(result, "ridge", "a result sharded over several GPUs is not supported")
+    outputs = _ridge_outputs(outputs)
+    arr = np.asarray(rows)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("rows must be a (B, 2) integer array of (first, count) with B >= 1, not %s of shape %r" % (arr.dtype, arr.shape))
+    arr = np.array([_row_range((int(a), int(b)), s, "rows[%d]" % k) for k, (a, b) in enumerate(arr)], dtype=np.int32)
+    e = _ridge_table(e, s, "e", True)
+    nu = _ridge_table(nu, s, "nu", False)
+    if isinstance(hz_per_cycle, (bool, np.bool_)) or not isinstance(hz_per_cycle, (int, float, np.integer, np.floating)):
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    with np.errstate(over="ignore"):
+        hz = np.float32(hz_per_cycle)
+    if not np.isfinite(hz) or not hz > 0:
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    seg = _ridge_segments(segments, n)
+    f32p = C.POINTER(C.c_float)
+    res = RidgeResult(None, c, arr, n, _pitch(n), outputs)
+    return _run_into(
+        res, "ridge", "%d channels, %d bands, %d columns, %s" % (c, len(arr), n, " + ".join(outputs)),
+        "fewer bands or fewer outputs per call",
+        lambda ptr: check(lib.gcwt_ridge(result.buffer.ptr, result.pitch, c, s, n, arr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         len(arr), e.ctypes.data_as(f32p), nu.ctypes.data_as(f32p), float(hz),
+                                         seg.ctypes.data_as(C.POINTER(C.c_int64)), len(seg), ptr.get("row"),
+                                         ptr.get("amplitude"), ptr.get("offset"), ptr.get("frequency"), res.pitch)))
 
 
 def _traces(buffer_ptr, pitch, n_traces, n_cols, what):

@@ -67,6 +67,26 @@ class _Bandpass:
         self.bands, self.rows, self.frequencies, self.time = bands, rows, frequencies, time
 
 
+class _Ridge:
+    """What ContinuousWaveletTransform.ridge returns (host arrays)."""
+
+    def __init__(self, row, amplitude, frequency, offset, bands, rows, frequencies, time, grid):
+        self.row, self.amplitude, self.frequency, self.offset = row, amplitude, frequency, offset
+        self.bands, self.rows, self.frequencies, self.time = bands, rows, frequencies, time
+        self._grid = grid                                    # the transform's frequencies, all rows
+
+    def grid_frequency(self):
+        """The frequency of the grid at the sub-row position ``row + offset``, ln f interpolated linearly between the
+        rows: float64, shaped like ``row``, NaN where ``row`` is -1.  NumPy on the host; needs the outputs 'row' and
+        'offset'."""
+        if self.row is None or self.offset is None:
+            raise ValueError("grid_frequency() needs the outputs 'row' and 'offset'")
+        at = self.row.astype(np.float64) + self.offset.astype(np.float64)
+        out = np.exp(np.interp(at, np.arange(self._grid.size, dtype=np.float64), np.log(self._grid)))
+        out[self.row < 0] = np.nan
+        return out
+
+
 class _Events:
     """What ContinuousWaveletTransform.detect returns (host arrays)."""
 
@@ -592,6 +612,52 @@ class ContinuousWaveletTransform(WaveletTransform):
         return _Bandpass(out.get("analytic"), out.get("envelope"), out.get("power"),
                          np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
                          [f[a:a + n] for a, n in rows], None if t is None else np.asarray(t))
+
+    def ridge(self, bands, *, outputs=("row", "amplitude", "frequency", "offset")):
+        """The spectral ridge of the last transform inside each band and the instantaneous frequency on it -- at which
+        frequency the rhythm is right now and how strong it is there: theta frequency against running speed, the drift
+        of a spindle, the chirp inside a ripple --, found on the device.  The transform must have been
+        ``output='complex'`` on one device.  ``bands``: one (f_lo, f_hi) pair in Hz or a sequence of B of them, resolved
+        as ``bandpass()`` resolves them; bands may overlap.  ``outputs``: which of 'row', 'amplitude', 'frequency',
+        'offset' to compute.  With w_r the coefficient of row r at a column, q_r = e_r |w_r|^2 and e =
+        engine.ridge_weights(frequencies, wavelet), the returned object has ``row`` (C, B, N) int32: the row of the
+        largest q_r among the band's rows, the lowest index among equal ones, and -1 where all are 0 (a gap between
+        epochs); ``amplitude`` (C, B, N) float32 = sqrt(q) there (0 in a gap): e makes a sinusoid of amplitude A on a
+        row's frequency read A, which for an energy-normalised Morlet transform also keeps the ridge from leaning to
+        low frequencies; ``offset`` (C, B, N) float32: the parabolic sub-row position of the maximum of q through the
+        winner's two neighbours, in rows, inside [-0.5, 0.5], exactly 0 on a band's first and last row and in a gap;
+        ``frequency`` (C, B, N) float32, Hz: the phase advance on the winning row from the column before to the
+        column after -- inside the column's own epoch (engine.segments_of), one-sided at its ends --, unwrapped
+        against the row's own frequency, so that an output stride K does not alias it; NaN in a gap and in an epoch
+        of one column.  Those not asked for are None.  Also ``bands`` (B, 2) as given, ``rows`` (B, 2) of (first,
+        count), ``frequencies``: a list of B arrays, ``time`` (N,), and ``grid_frequency()``: ln f of the grid
+        interpolated at row + offset, on the host and on request, NaN in a gap.  After the reference's single-channel
+        call the channel axis is dropped, the band axis always stays.  ``row``, ``amplitude`` and ``offset`` are
+        prescribed single float32 operations and ``frequency`` all but its arctangent (include/ghostcwt.h:
+        gcwt_ridge): a band has the same bits alone and among any others.  What the ridge does not do: there is no
+        chaining across columns -- every column is ranked on its own --; there is one maximum per band, so two rhythms
+        in one band need two bands; and where the two largest rows are nearly equal, ``row`` (with ``offset`` and
+        ``grid_frequency()``) flickers between them while ``frequency`` does not.  Only the ridge crosses to the host;
+        the resident result, ``fetch()`` and the result attributes are untouched."""
+        from .. import engine
+        result, squeeze = self._resident_rows("ridge")
+        f = np.array(self._frequencies)
+        rows = engine.band_rows(bands, f)
+        stride, fs = self._stride, float(self._fs)
+        t = self.time
+        t = None if t is None else np.asarray(t)
+        segments = engine.segments_of(t, stride / fs, fs, result.shape[2])
+        res = engine.ridge(result, rows, engine.ridge_weights(f, self._wavelet), 2 * np.pi * f * stride / fs, fs / stride,
+                           segments, outputs)
+        try:
+            out = res.to_host()
+        finally:
+            res.free()
+        if squeeze:
+            out = {k: v[0] for k, v in out.items()}
+        return _Ridge(out.get("row"), out.get("amplitude"), out.get("frequency"), out.get("offset"),
+                      np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
+                      [f[a:a + n] for a, n in rows], t, f)
 
     def detect(self, band, *, on="envelope", threshold=3.0, edge=0.0, units="sd", min_duration=0.0, max_duration=None,
                min_gap=0.0, stats="mean", baseline=None, smooth=None, combine=False):

@@ -320,6 +320,50 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
 int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
                   const int32_t* bands, int32_t n_bands, const float* g, const float* h,
                   float* d_analytic, float* d_envelope, float* d_power, int64_t out_pitch);
+/* The spectral ridge of each band of a device-resident complex result and the instantaneous frequency on it, on the
+ * device that holds the rows (csrc/ridge.hip): per column the row of largest weighted modulus in the band, and the rate
+ * of phase advance on that row.  d_rows, pitch and n_cols are those of gcwt_coherence.  bands: n_bands (first, count)
+ * pairs in HOST memory as for gcwt_bandpass; bands may overlap and repeat.  e: n_scales float32 weights in HOST memory,
+ * finite and > 0, which make rows comparable (ghost_amd.engine.ridge_weights makes them so that a sinusoid of amplitude
+ * A on a row's frequency reads amplitude = A there).  nu: n_scales float32 in HOST memory, finite and >= 0: the phase
+ * advance row r expects per column, 2 pi f_r K / fs with the output stride K.  hz_per_cycle: fs / K, finite and > 0.
+ * segments: n_segments (start, stop) pairs in HOST memory, ascending, each holding a column and starting where the one
+ * before stops, the first at 0 and the last ending at n_cols (ghost_amd.engine.segments_of): the stretches of columns
+ * that belong together on the clock.  The entry copies the tables to the device and frees the copy.  For every channel
+ * c, band b (rows first .. first + R - 1) and column t, every operation a single correctly rounded float32 one and no
+ * product contracted into a sum that is not written as fmaf:
+ *   q_r = e[r] * fmaf(w.im, w.im, w.re * w.re), w = W[c][r][t], the rows walked in ascending r.  The winner is the first
+ *     row whose q is larger than every earlier one and than 0: the lowest index among equal maxima.  Where every q_r
+ *     is 0 (a gap between epochs) there is no winner.
+ *   d_row [C][n_bands][n_cols]        int32    the winner's row index in [0, n_scales), or -1
+ *   d_amplitude [C][n_bands][n_cols]  float32  sqrt(q_win); 0 with no winner
+ *   d_offset [C][n_bands][n_cols]     float32  the parabolic sub-row position of the maximum of q, in rows: with qm, qp
+ *     the q of rows row - 1 and row + 1,  d1 = qm - qp;  s = qm + qp;  d2 = s - 2 * q_win;  offset = (0.5f * d1) / d2.
+ *     Exactly 0 where the winner is the band's first or last row, where d2 == 0, and with no winner; otherwise inside
+ *     [-0.5, 0.5] up to the rounding of d1 and d2 (q_win >= qm, qp)
+ *   d_frequency [C][n_bands][n_cols]  float32  Hz: with [start, stop) the segment that holds t, tm = max(t - 1, start), tp
+ *     = min(t + 1, stop - 1), span = tp - tm (0, 1 or 2), a = W[c][row][tp], b = W[c][row][tm], T = float32(2 pi):
+ *       re = fmaf(a.re, b.re, a.im * b.im)    im = fmaf(a.im, b.re, -(a.re * b.im))    dphi = atan2f(im, re)
+ *       k = rintf(((float)span * nu[row] - dphi) / T)      num = dphi + T * k
+ *       scale = hz_per_cycle / (T * (float)span)           frequency = num * scale
+ *     k unwraps the advance against the row's own frequency, so an output stride does not alias the result.  NaN where
+ *     row == -1, where span == 0 (a segment of one column), and where re and im are both 0.  The arctangent is the
+ *     device library's (within 2e-6 rad, measured: profiles/ridge.md); everything else is counted:
+ *     tests/ridge_model.py has the bound.
+ * A cell depends on nothing but its own band's rows at the columns tm, t and tp: a band gives the same bits alone and
+ * among any others, in any order, at any column count or pitch and whichever outputs are asked for, and two runs agree
+ * in bits.  There is no chaining of the ridge across columns and one maximum per band: two rhythms in one band need two
+ * bands; where the two largest rows are nearly equal the row flickers between them while frequency does not.  Any
+ * output may be NULL, but not all; their rows are out_pitch (>= n_cols) elements apart.  Without d_frequency neither
+ * the neighbours are fetched nor the arctangent made.  A workgroup takes GCWT_RIDGE_TILE_COLS columns, counted from
+ * column 0, of GCWT_RIDGE_GROUP_BANDS consecutive bands of the list.  Plan-independent; the device is the one that
+ * holds d_rows.  Arguments -- every band, weight, nu entry and segment among them -- are checked before any device call
+ * (GCWT_ERR_INVALID; the message names the first offending index). */
+enum { GCWT_RIDGE_TILE_COLS = 512, GCWT_RIDGE_GROUP_BANDS = 4 };
+int gcwt_ridge(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+               const int32_t* bands, int32_t n_bands, const float* e, const float* nu, float hz_per_cycle,
+               const int64_t* segments, int64_t n_segments,
+               int32_t* d_row, float* d_amplitude, float* d_offset, float* d_frequency, int64_t out_pitch);
 /* The steps of threshold-crossing detection on float32 traces that lie on a device (csrc/detect_runs.hip): n_traces
  * rows of n_cols (1 .. 2^40 - 1) live columns, pitch (>= n_cols) elements apart -- what gcwt_bandpass leaves in
  * d_envelope / d_power with n_traces = C * n_bands, or any row of an amplitude result.  All are plan-independent and
