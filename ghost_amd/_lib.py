@@ -150,6 +150,7 @@ def _load():
         "gcwt_debug_bandpass_grid": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, i64p, i32p, i64p]),
         "gcwt_debug_fetch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int64]),
         "gcwt_debug_scale_lists": (C.c_int, [vp, i32p, i32p, i32p, i32p, C.c_int32]),
+        "gcwt_debug_work_items": (C.c_int, [vp, C.c_int, C.c_int, i32p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

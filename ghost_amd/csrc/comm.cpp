@@ -13,6 +13,7 @@
 #include <string>
 
 #include "errors.h"
+#include "plan_state.h"
 
 // minimal RCCL surface (matches rccl.h / nccl.h ABI)
 typedef struct ncclComm* ncclComm_t;
@@ -20,10 +21,6 @@ typedef struct { char internal[128]; } ncclUniqueId;
 typedef int ncclResult_t;
 enum { kNcclUint8 = 1, kNcclFloat64 = 8 };
 enum { kNcclMax = 2 };
-
-float2* gcwt_internal_bank_ptr(gcwt_plan* p, size_t* bytes);
-hipStream_t gcwt_internal_stream(gcwt_plan* p);
-int gcwt_internal_refresh_bank(gcwt_plan* p);
 
 namespace {
 
@@ -188,12 +185,12 @@ int gcwt_comm_broadcast_bank(gcwt_comm* c, gcwt_plan* plan, int root) {
   if (rc) return rc;
   // the plan's bank lives on the plan's device; the communicator must have been made on the same one
   hipPointerAttribute_t attr;
-  size_t bytes = 0;
-  float2* bank = gcwt_internal_bank_ptr(plan, &bytes);
+  float2* bank = plan->d_bank;
+  const size_t bytes = sizeof(float2) * (size_t)plan->hp.prm.n_freqs * plan->hp.block;
   if (hipPointerGetAttributes(&attr, bank) == hipSuccess && attr.device != c->device)
     return fail(GCWT_ERR_INVALID, "the plan and the communicator are on different devices");
   if (hipSetDevice(c->device) != hipSuccess) return fail(GCWT_ERR_HIP, "the communicator's device cannot be selected");
-  hipStream_t st = gcwt_internal_stream(plan);
+  hipStream_t st = plan->stream;
   const ncclResult_t nr = rccl().Broadcast(bank, bank, bytes, kNcclUint8, root, c->comm, st);
   if (nr != 0) return nccl_fail("ncclBroadcast", nr);
   if ((rc = gcwt_internal_refresh_bank(plan))) return rc;   // signed gain table follows the bank

@@ -1328,6 +1328,30 @@ class CwtPlan:
         return [{"rows": rows[first[l]:first[l + 1]].copy(), "n_plain": int(plain[l]),
                  "j_hi": j_hi[first[l]:first[l + 1]].copy()} for l in range(n_lv)]
 
+    def debug_work_items(self, kernel, batch=0):
+        """The workgroup items of one synthesis kernel for launch batch ``batch`` (an index into ``debug_batches``),
+        as the upload sends them (include/ghostcwt_debug.h: gcwt_debug_work_items; no device needed).  ``kernel``:
+        "synth16", "synth7", "synth7_wide", "synth7_narrow", "interp" or "pipelined".  Returns {"items": a structured
+        array, one record per item in launch order, "split": for "interp" / "pipelined" how many of them the first
+        of the two launches takes, else None}."""
+        fields = {"synth16": (0, ("level", "scale", "blk0", "nblk")),
+                  "synth7": (1, ("level", "blk0", "rtile", "pad")),
+                  "synth7_wide": (2, ("level", "blk0", "rtile", "pad")),
+                  "synth7_narrow": (3, ("level", "blk0", "rtile", "pad")),
+                  "interp": (4, ("level", "blk0", "pass0", "n_pass", "lo", "hi")),
+                  "pipelined": (5, ("level", "blk0", "round0", "n_rounds"))}
+        code, names = fields[kernel]
+        n = lib.gcwt_debug_work_items(self._handle, code, int(batch), None, 0)
+        if n < 0:
+            check(n)
+        flat = np.zeros(max(1, n), np.int32)
+        rc = lib.gcwt_debug_work_items(self._handle, code, int(batch), flat.ctypes.data_as(C.POINTER(C.c_int32)), n)
+        if rc < 0:
+            check(rc)
+        head = 1 if code >= 4 else 0
+        items = np.ascontiguousarray(flat[head:n]).view(np.dtype([(f, np.int32) for f in names]))
+        return {"items": items, "split": int(flat[0]) if head else None}
+
     def debug_mean_folded(self):
         """True when the last run summed the channels inside the forward column pass (include/ghostcwt_debug.h)."""
         return bool(lib.gcwt_debug_mean_folded(self._handle))

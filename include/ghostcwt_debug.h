@@ -72,6 +72,25 @@ int gcwt_debug_fetch(gcwt_plan* plan, int what, int channel, int epoch, int leve
  * be NULL.  Returns the number of entries; row and j_hi are filled only when max_entries holds them. */
 int gcwt_debug_scale_lists(gcwt_plan* plan, int32_t* level_first, int32_t* level_plain, int32_t* row,
                            int32_t* j_hi, int32_t max_entries);
+/* The workgroup items of one synthesis kernel for launch batch `batch` (0 .. in the order of gcwt_debug_batch_of),
+ * exactly as gcwt_plan_upload sends them and in that order (csrc/work_items.h), as flat int32 records:
+ *   SYNTH16                  level, scale, blk0, nblk
+ *   SYNTH7, _WIDE, _NARROW   level, blk0, rtile, 0        (k_synth7, its wide-halo and its 16-column list)
+ *   INTERP                   one value first, the number of items of the first launch (the levels below option
+ *                            interp_split_r); then level, blk0, pass0, n_pass, wt_lo, wt_hi
+ *   PIPELINED                one value first, the number of items of the first launch (I > 4; the second: I = 4);
+ *                            then level, blk0, round0, n_rounds
+ * Needs no device and no upload.  Returns the number of int32 values (out is filled only when max_ints holds them;
+ * out may be NULL), or a negative error. */
+enum gcwt_debug_items {
+  GCWT_DEBUG_ITEMS_SYNTH16 = 0,
+  GCWT_DEBUG_ITEMS_SYNTH7 = 1,
+  GCWT_DEBUG_ITEMS_SYNTH7_WIDE = 2,
+  GCWT_DEBUG_ITEMS_SYNTH7_NARROW = 3,
+  GCWT_DEBUG_ITEMS_INTERP = 4,
+  GCWT_DEBUG_ITEMS_PIPELINED = 5
+};
+int gcwt_debug_work_items(const gcwt_plan* plan, int kernel, int batch, int32_t* out, int32_t max_ints);
 /* The exact (real) response G of one scale's reference kernel at theta = 2 pi a[i] / b,
  * i < n, evaluated on the HOST by the same code the device bank builder runs
  * (csrc/morse_exact.h).  Needs no GPU. */

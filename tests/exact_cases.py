@@ -318,7 +318,7 @@ def bc_row(xm, epochs, hop, back, h, ramp=0, single=False, late_block=None, swap
 
 
 def launch_chunks(epochs, hop, chunk):
-    """RESTATEMENT of api.cpp's flush of the block convolution for a whole-recording execute: per launch batch of up
+    """RESTATEMENT of pipeline.cpp's flush of the block convolution for a whole-recording execute: per launch batch of up
     to sixteen epochs the blocks are numbered through (``blk_first``) and launched ``chunk`` at a time.  Returns
     [(epoch index, position in the epoch's blocks)] of every block that is the FIRST of a launch after the first of its
     batch -- the blocks on a chunk seam."""

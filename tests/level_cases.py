@@ -31,7 +31,7 @@ Cases 1, 4, 5, 6, 9 also run with precision = 'fast' (no low cut, the float32 fo
 slow_fft = 1 (the generic kernels at every size).
 
 Not reached by any plan: k_fft_colsq<-1,true,1|2>.  launch_fft_cols_segs takes them for real input only when a segment
-of the batch has no valid sample, and api.cpp never puts such a segment into a batch (n_valid is the segment's ne > 0;
+of the batch has no valid sample, and pipeline.cpp never puts such a segment into a batch (n_valid is the segment's ne > 0;
 segments with nothing to write are skipped before).  ``forward_kernels`` names them for ``all_nonempty=False``."""
 import numpy as np
 from scipy.fft import fft, ifft
@@ -129,7 +129,7 @@ def _cols_name(sign, real_in, length, slow_fft):
 
 
 def level_kernels(p1, decimation, long_a=1, band_shift=0, slow_fft=False):
-    """RESTATEMENT of the level branch of api.cpp's execute ("lp.decimation / A <= kMaxTwoPassDecimation") with
+    """RESTATEMENT of the level branch of pipeline.cpp's level_pass ("lp.decimation / A <= kMaxTwoPassDecimation") with
     launch_fft_rows and launch_fft_cols_segs of csrc/kernels.hip: the kernels that make x_R of one level from the stored
     spectrum of p1 rows, in launch order.  A change to that dispatch must change this too."""
     r = decimation // long_a                      # decimation of the STORED spectrum
@@ -146,7 +146,7 @@ def level_kernels(p1, decimation, long_a=1, band_shift=0, slow_fft=False):
 
 
 def hermitian(p1, fullband, slow_fft=False):
-    """api.cpp: rows 0 .. P1/2 of the spectrum are built and the others written as their reflections."""
+    """pipeline.cpp: rows 0 .. P1/2 of the spectrum are built and the others written as their reflections."""
     return (not slow_fft) and p1 >= 4 and not fullband
 
 

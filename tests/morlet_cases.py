@@ -82,7 +82,7 @@ def levels(plan):
 
 
 def kernel(level, synth16=False):
-    """The synthesis kernel of a Morlet plan's level (api.cpp: level_kernel; no interpolating synthesis):
+    """The synthesis kernel of a Morlet plan's level (work_items.cpp: level_kernel; no interpolating synthesis):
     "k_synth", "k_synth7" or "k_synth7w" (the WIDE instantiation: halo > 48, shifted bands only)."""
     if level["band_shift"] == 0 and (synth16 or level["halo"] > 48 or level["scales"].size > 256):
         return "k_synth"

@@ -187,14 +187,14 @@ def phase_tiles(decimation, cols):
 
 
 def block_groups(lv, cols):
-    """Workgroups along the blocks of a level (api.cpp: bpb = max(1, cols / R))."""
+    """Workgroups along the blocks of a level (work_items.cpp: bpb = max(1, cols / R))."""
     bpb = max(1, cols // lv["decimation"])
     return -(-lv["nblk"] // bpb), lv["nblk"] % bpb
 
 
 def early_groups(plan, cols, narrow_r=2):
     """RESTATEMENT of the test a k_synth7 workgroup makes first (synth.hip: "leave at once if this group of blocks keeps
-    no sample inside this segment's window") and of how api.cpp cuts a level into groups of blocks: per level that
+    no sample inside this segment's window") and of how work_items.cpp cuts a level into groups of blocks: per level that
     holds scales {decimation: [groups of segment 0, 1, ... that leave, of how many]}.  The level grids are those of
     the batch (the union of its segments' own), a segment's window is [lead, lead + its samples), a group of
     max(1, columns / R) blocks keeps the samples [blk0 hop R, (blk0 + blocks) hop R); levels up to ``narrow_r`` take

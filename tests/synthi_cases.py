@@ -1,6 +1,6 @@
 """Shared pieces of the interpolating-synthesis tests (plain module, no fixtures, no GPU): the cases that between them
 reach every data-dependent branch of k_synthi (csrc/synthi.hip), what a plan reaches read off the planner's hooks, a
-restatement of how api.cpp cuts a level into workgroup items, and the float64 model / oracle rows of a case, computed
+restatement of how work_items.cpp cuts a level into workgroup items, and the float64 model / oracle rows of a case, computed
 once (tests/test_synthi_cases_cpu.py pins the planner's decisions, tests/test_gpu_synthi_matrix.py runs the cases).
 
 Case   plan                                                        what it is there for
@@ -96,8 +96,8 @@ def designs(plan):
 
 
 def clamp_lgnb(decimation, q, lgnb=None):
-    """Blocks per workgroup (log2) of a level: api.cpp's default, the forced value of option interp_lgnb, and the
-    clamp (q << lgnb) <= 16 (gcwt_plan_upload_impl, "Blocks per workgroup")."""
+    """Blocks per workgroup (log2) of a level: work_items.cpp's default, the forced value of option interp_lgnb, and the
+    clamp (q << lgnb) <= 16 (synthi_items, "Blocks per workgroup")."""
     v = (1 if decimation <= 32 and q <= 2 else 0) if lgnb is None else min(int(lgnb), 2)
     while v > 0 and (q << v) > K_COLS:
         v -= 1
@@ -125,9 +125,10 @@ def switches(seq):
 
 
 def items(plan, lgnb=None, batch=0):
-    """RESTATEMENT of how gcwt_plan_upload_impl (csrc/api.cpp, "A workgroup walks all the scales of its blocks unless
-    that is too much for one": the loop over `attempt` that halves `target`) cuts the interpolated levels of one launch
-    batch into workgroup items.  A change to that cut must change this too.  Used only to assert that a case has items
+    """RESTATEMENT of how synthi_items (csrc/work_items.cpp, "A workgroup walks all the scales of its blocks unless
+    that is too much for one"; cut_largest_first halves `target`) cuts the interpolated levels of one launch batch
+    into workgroup items.  A change to that cut must change this too: tests/test_synthi_cases_cpu.py holds the two
+    together through ``debug_work_items``.  Used only to assert that a case has items
     of several parts, items that start after the level's first pass and levels walked in one pass, and to place test
     windows inside / across the parts.
 
@@ -181,7 +182,7 @@ def branches(plan):
             continue
         rows = np.flatnonzero(lof == l)
         even = (si["length"][rows] % 2 == 0)
-        rows = np.concatenate([rows[~even], rows[even]])              # api.cpp: odd kernel lengths first
+        rows = np.concatenate([rows[~even], rows[even]])              # work_items.cpp: odd kernel lengths first
         par = [int(si["length"][r] % 2 == 0) for r in rows]
         lgi4 = int(np.log2(d["factor"] // 4))
         cut = {}

@@ -134,7 +134,7 @@ def test_case_b_batches_on_both_sides_of_the_grid_limit(option, c, batch_bytes, 
     assert all(seg[2] == 4096 for seg in p.segments()) and len(p.segments()) == 20
     assert si["method"].tolist() == [1, 0, 0] and si["decimation"].tolist() == [1, 4, 4]
     assert p.debug_batches() == batches
-    # 65535 / C epochs per batch, and the direct path's launches flushed at the same count (api.cpp: (ne + 1) C > 65535)
+    # 65535 / C epochs per batch, and the direct path's launches flushed at the same count (pipeline.cpp: (ne + 1) C > 65535)
     assert batches[0][1] == min(16, 65535 // c)
     assert p.info["out_bytes"] == c * 3 * cc.B_N * 4
     if c >= 4369:

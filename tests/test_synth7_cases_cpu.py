@@ -226,3 +226,31 @@ def test_what_the_stage_comparison_catches(plan_of):
         short.append(err(row(np.where(k >= 16 * (j_hi - 1), 0, h)), r))
     print("first layer one input too short: %.3g .. %.3g, %d of %d rows over the cap" % (
         min(short), max(short), sum(v > s7.STAGE_CAP for v in short), len(short)))
+
+
+@pytest.mark.parametrize("narrow_r", (0, 2))
+@pytest.mark.parametrize("cols", (16, 32))
+@pytest.mark.parametrize("name", list(s7.CASES))
+def test_restated_groups_are_the_librarys_items(plan_of, option, name, cols, narrow_r):
+    """``block_groups`` x ``phase_tiles`` against the items the library cuts (``debug_work_items``: what the upload
+    sends), per level and per list -- the 16-column list of the levels up to synth7_narrow_r in a 32-column plan, the
+    wide-halo list (halo > 48), the plain one -- and every item's first block a multiple of the blocks per group."""
+    option("synth_cols", cols)
+    option("synth7_narrow_r", narrow_r)
+    output = s7.CASES[name]["outputs"][0]
+    plan = plan_of(name, output)
+    got = {k: plan.debug_work_items(k)["items"] for k in ("synth7", "synth7_wide", "synth7_narrow")}
+    total = 0
+    for lv in s7.levels(plan):
+        on7 = lv["kernel"].startswith("k_synth7")
+        narrow = cols == 32 and lv["decimation"] <= narrow_r and lv["halo"] <= 48
+        mine = "synth7_wide" if lv["halo"] > 48 else "synth7_narrow" if narrow else "synth7"
+        c = 16 if narrow else cols
+        want = s7.block_groups(lv, c)[0] * s7.phase_tiles(lv["decimation"], c) if on7 else 0
+        for k, items in got.items():
+            its = items[items["level"] == lv["level"]]
+            assert its.size == (want if k == mine else 0), (name, lv["decimation"], k)
+            assert not (its["blk0"] % max(1, c // lv["decimation"])).any()
+            assert not its.size or sorted(set(its["rtile"].tolist())) == list(range(s7.phase_tiles(lv["decimation"], c)))
+        total += want
+    assert total == sum(items.size for items in got.values()) and total > 0

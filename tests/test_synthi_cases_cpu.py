@@ -1,5 +1,5 @@
 """The cases of tests/synthi_cases.py on the host: the planner takes each of them to the branch of k_synthi it is there
-for, and the float64 model agrees with the oracle on every row.  A change to the planner or to api.cpp's cut that moves
+for, and the float64 model agrees with the oracle on every row.  A change to the planner or to work_items.cpp's cut that moves
 a case off its branch fails here, not silently on the GPU.  No device."""
 import numpy as np
 import pytest
@@ -135,3 +135,33 @@ def test_model_matches_oracle_on_every_row(name):
     err = rel_err(sc.model(name), sc.oracle(name))
     print(name, "model against oracle, worst row %.3g" % err.max())
     assert err.shape == (len(sc.CASES[name]["f"]),) and err.max() < sc.MODEL_CPU, err
+
+
+@pytest.mark.parametrize("split_r", (0, 64))
+@pytest.mark.parametrize("lgnb", (None, 0, 1, 2))
+@pytest.mark.parametrize("name,n_channels", [(n, 1) for n in sc.CASES] + [("C", 40)])
+def test_restated_cut_is_the_librarys(option, name, n_channels, lgnb, split_r):
+    """``synthi_cases.items`` -- what the GPU matrix places its windows by -- against the items the library cuts
+    (``debug_work_items``: what the upload sends), field by field, under every forced number of blocks per workgroup
+    and with one launch or two.  The upload orders the list: the levels below interp_split_r first, then by output
+    bytes, largest first, ties in the order of the cut.  Case C at 1 and at 40 channels: `target` halved and not."""
+    if lgnb is not None:
+        option("interp_lgnb", lgnb)
+    option("interp_split_r", split_r)
+    plan = sc.make_plan(name, n_channels=n_channels)
+    its, _ = sc.items(plan, lgnb)
+    levels, di = plan.debug_levels(), plan.debug_interp()["levels"]
+
+    def out_bytes(it):
+        lv, q = levels[it["level"]], di[it["level"]]["q"]
+        nb = 1 << sc.clamp_lgnb(lv["decimation"], q, lgnb)
+        pass_bytes = (sc.K_COLS // (q * nb)) * nb * lv["hop"] * lv["decimation"] * 4
+        return it["n_pass"] * pass_bytes * (it["hi"] - it["lo"]) // max(1, it["wps"])
+    its = sorted(its, key=lambda it: (it["decimation"] >= split_r, -out_bytes(it)))
+    got = plan.debug_work_items("interp")
+    assert got["items"].size == len(its) > 0
+    for field in ("level", "blk0", "pass0", "n_pass", "lo", "hi"):
+        assert got["items"][field].tolist() == [it[field] for it in its], (name, field)
+    assert got["split"] == sum(it["decimation"] < split_r for it in its)
+    if name in ("B", "E", "F28"):                         # levels on both sides of R = 64
+        assert (0 < got["split"] < len(its)) == (split_r == 64)
