@@ -23,6 +23,7 @@ ERR_INVALID, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_COMM, ERR_C
 COMM_ID_BYTES = 128
 SMOOTH_MAX_HALF = 4096                              # GCWT_SMOOTH_MAX_HALF
 COUPLING_SURROGATES_MAX_WINDOW = 2048               # GCWT_COUPLING_SURROGATES_MAX_WINDOW
+SQUEEZE_TILE_COLS, SQUEEZE_GROUP_CELLS, SQUEEZE_MAX_CELLS = 512, 16, 4096    # GCWT_SQUEEZE_*
 
 
 class GhostCwtError(RuntimeError):
@@ -93,6 +94,8 @@ def _load():
                                     C.c_int64]),
         "gcwt_ridge": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, f32p, f32p, C.c_float, i64p,
                                  C.c_int64, vp, vp, vp, vp, C.c_int64]),
+        "gcwt_squeeze": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, f32p, f32p, f32p,
+                                   C.c_float, i64p, C.c_int64, f32p, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64]),
         "gcwt_trace_stats": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "gcwt_trace_runs": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, C.c_int64, vp, vp, vp, vp, i64p]),
         "gcwt_trace_order": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, f32p, i64p, C.c_int32, i64p, f32p]),

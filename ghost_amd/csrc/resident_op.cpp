@@ -1,6 +1,7 @@
 // resident_op.cpp -- the host side every row operator shares (resident_op.h).
 #include "resident_op.h"
 
+#include <cmath>
 #include <string>
 
 #include "errors.h"
@@ -26,6 +27,35 @@ int check_window(const char* op, int64_t window) {
 int check_row_range(const char* op, const char* noun, int32_t first, int32_t count, int32_t n_scales) {
   if (first < 0 || count < 1 || count > n_scales - first)
     return fail(GCWT_ERR_INVALID, std::string(op) + ": the " + noun + " must be a non-empty range inside [0, n_scales)");
+  return GCWT_OK;
+}
+
+int check_table(const char* op, const char* name, const float* w, int32_t n_scales, bool strict) {
+  for (int32_t r = 0; r < n_scales; ++r)
+    if (!std::isfinite(w[r]) || (strict ? !(w[r] > 0.f) : w[r] < 0.f))
+      return fail(GCWT_ERR_INVALID, std::string(op) + ": " + name + "[" + std::to_string(r) + "] must be finite and " +
+                                        (strict ? "above 0" : "at least 0"));
+  return GCWT_OK;
+}
+
+int check_segments(const char* op, const int64_t* segments, int64_t n_segments, int64_t n_cols) {
+  int64_t end = 0;                                           // where the segment before this one stops
+  for (int64_t i = 0; i < n_segments; ++i) {
+    const int64_t start = segments[2 * i], stop = segments[2 * i + 1];
+    const std::string which = std::string(op) + ": segments[" + std::to_string(i) + "] = [" + std::to_string(start) + ", " +
+                              std::to_string(stop) + ")";
+    if (stop <= start) return fail(GCWT_ERR_INVALID, which + " holds no column");
+    if (start != end)
+      return fail(GCWT_ERR_INVALID, which + (start < end ? " starts before" : " leaves columns uncovered after") +
+                                        " the end of the segment before it at " + std::to_string(end) +
+                                        ": ascending, disjoint segments that cover [0, n_cols)");
+    if (stop > n_cols) return fail(GCWT_ERR_INVALID, which + " ends past n_cols = " + std::to_string(n_cols));
+    end = stop;
+  }
+  if (end != n_cols)
+    return fail(GCWT_ERR_INVALID, std::string(op) + ": segments[" + std::to_string(n_segments - 1) + "] stops at " +
+                                      std::to_string(end) + " and leaves the columns up to n_cols = " + std::to_string(n_cols) +
+                                      " uncovered");
   return GCWT_OK;
 }
 

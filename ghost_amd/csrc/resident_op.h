@@ -17,6 +17,10 @@ int check_rows(const char* op, int32_t n_scales, int64_t n_cols, int64_t pitch);
 int check_window(const char* op, int64_t window);
 // `noun`: what the message calls the range ("rows", "phase rows", ...)
 int check_row_range(const char* op, const char* noun, int32_t first, int32_t count, int32_t n_scales);
+// a per-row table `name` of n_scales float32: every entry finite and, with strict, > 0, else >= 0
+int check_table(const char* op, const char* name, const float* w, int32_t n_scales, bool strict);
+// (start, stop) pairs: ascending, each holding a column and starting where the one before stops, from 0 to n_cols
+int check_segments(const char* op, const int64_t* segments, int64_t n_segments, int64_t n_cols);
 
 // d_rows must be device memory and every non-NULL output memory of the same device; on GCWT_OK that device is the
 // calling thread's, from here on.

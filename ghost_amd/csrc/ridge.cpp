@@ -32,35 +32,6 @@ int cut(int32_t n_channels, int64_t n_cols, int32_t n_bands, gcwt::RgArgs* a) {
   return GCWT_OK;
 }
 
-// strict: > 0, else >= 0
-int check_table(const char* name, const float* w, int32_t n_scales, bool strict) {
-  for (int32_t r = 0; r < n_scales; ++r)
-    if (!std::isfinite(w[r]) || (strict ? !(w[r] > 0.f) : w[r] < 0.f))
-      return fail(GCWT_ERR_INVALID, std::string("gcwt_ridge: ") + name + "[" + std::to_string(r) + "] must be finite and " +
-                                        (strict ? "above 0" : "at least 0"));
-  return GCWT_OK;
-}
-
-// ascending, each holding a column and starting where the one before stops, from 0 to n_cols
-int check_segments(const int64_t* segments, int64_t n_segments, int64_t n_cols) {
-  int64_t end = 0;                                           // where the segment before this one stops
-  for (int64_t i = 0; i < n_segments; ++i) {
-    const int64_t start = segments[2 * i], stop = segments[2 * i + 1];
-    const std::string which = "gcwt_ridge: segments[" + std::to_string(i) + "] = [" + std::to_string(start) + ", " + std::to_string(stop) + ")";
-    if (stop <= start) return fail(GCWT_ERR_INVALID, which + " holds no column");
-    if (start != end)
-      return fail(GCWT_ERR_INVALID, which + (start < end ? " starts before" : " leaves columns uncovered after") +
-                                        " the end of the segment before it at " + std::to_string(end) +
-                                        ": ascending, disjoint segments that cover [0, n_cols)");
-    if (stop > n_cols) return fail(GCWT_ERR_INVALID, which + " ends past n_cols = " + std::to_string(n_cols));
-    end = stop;
-  }
-  if (end != n_cols)
-    return fail(GCWT_ERR_INVALID, "gcwt_ridge: segments[" + std::to_string(n_segments - 1) + "] stops at " + std::to_string(end) +
-                                      " and leaves the columns up to n_cols = " + std::to_string(n_cols) + " uncovered");
-  return GCWT_OK;
-}
-
 bool on16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
@@ -86,12 +57,12 @@ extern "C" int gcwt_ridge(const float* d_rows, int64_t pitch, int32_t n_channels
       rc = check_row_range(kOp, ("band " + std::to_string(k)).c_str(), bands[2 * k], bands[2 * k + 1], n_scales);
       if (rc) return rc;
     }
-    rc = check_table("e", e, n_scales, true);
-    if (!rc) rc = check_table("nu", nu, n_scales, false);
+    rc = check_table(kOp, "e", e, n_scales, true);
+    if (!rc) rc = check_table(kOp, "nu", nu, n_scales, false);
     if (rc) return rc;
     if (!std::isfinite(hz_per_cycle) || !(hz_per_cycle > 0.f)) return fail(GCWT_ERR_INVALID, "gcwt_ridge: hz_per_cycle must be finite and above 0");
     if (n_segments > n_cols) return fail(GCWT_ERR_INVALID, "gcwt_ridge: more segments than columns");
-    rc = check_segments(segments, n_segments, n_cols);
+    rc = check_segments(kOp, segments, n_segments, n_cols);
     if (rc) return rc;
     if (out_pitch < n_cols) return fail(GCWT_ERR_INVALID, "gcwt_ridge: out_pitch is below n_cols");
     a.pitch = pitch; a.n_scales = n_scales;

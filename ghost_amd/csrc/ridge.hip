@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "phase_advance.h"
 #include "ridge.h"
 #include "wave_reduce.h"
 
@@ -50,7 +51,6 @@ namespace gcwt {
 namespace {
 
 constexpr int kRgDepth = 4;                                 // rows whose loads are in flight
-constexpr float kTwoPi = 6.28318530717958647692f;
 
 struct Best { float q, qm, qp; int row; };
 
@@ -74,25 +74,15 @@ __device__ __forceinline__ float ridge_offset(const Best& s, int first, int end)
   return d2 == 0.f ? 0.f : __fdiv_rn(__fmul_rn(0.5f, d1), d2);
 }
 
-// chan: the channel's rows; [start, stop): the segment of column t, which holds it
+// chan: the channel's rows; [start, stop): the segment of column t, which holds it (phase_advance.h has the arithmetic)
 __device__ __forceinline__ float ridge_frequency(const RgArgs& a, const float2* chan, Const<float> nu, int row, int64_t t,
                                                  int64_t start, int64_t stop) {
-  const float nan = __builtin_nanf("");
-  if (row < 0) return nan;
+  if (row < 0) return __builtin_nanf("");
   const int64_t tm = std::max(t - 1, start), tp = std::min(t + 1, stop - 1);   // (start <= t < stop <= n_cols)
   const int span = (int)(tp - tm);
-  if (span == 0) return nan;
+  if (span == 0) return __builtin_nanf("");
   const float2* w = chan + (int64_t)row * a.pitch;
-  const float2 x = w[tp], y = w[tm];
-  const float re = fmaf(x.x, y.x, __fmul_rn(x.y, y.y));
-  const float im = fmaf(x.y, y.x, -__fmul_rn(x.x, y.y));
-  if (re == 0.f && im == 0.f) return nan;
-  const float dphi = atan2f(im, re);
-  const float span_f = (float)span;
-  const float k = rintf(__fdiv_rn(__fsub_rn(__fmul_rn(span_f, nu[row]), dphi), kTwoPi));
-  const float num = __fadd_rn(dphi, __fmul_rn(kTwoPi, k));
-  const float scale = __fdiv_rn(a.hz_per_cycle, __fmul_rn(kTwoPi, span_f));
-  return __fmul_rn(num, scale);
+  return phase_advance_hz(w[tp], w[tm], span, nu[row], a.hz_per_cycle);
 }
 
 // FULL: all kRgCols columns of the tile exist.  ALIGNED: RgArgs::aligned

@@ -804,6 +804,125 @@ def ridge(result, rows, e, nu, hz_per_cycle, segments, outputs=("row", "amplitud
                                          ptr.get("amplitude"), ptr.get("offset"), ptr.get("frequency"), res.pitch)))
 
 
+def squeeze_edges(centres):
+    """The cells of squeeze() around the centre frequencies ``centres`` (Hz, positive, strictly monotonic, at least 2 and at
+    most 4096): -> (edges, descending).  ``edges``: float32, L + 1 entries, ascending: the geometric midpoints between
+    neighbouring centres, the two ends extended by half their one-sided step in ln f; computed in float64 and cast once.
+    ``descending``: the centres fall, so the cell of ``centres[k]`` is cell L - 1 - k of the ascending edges.  Host only.
+    ValueError where the cast leaves two edges equal: it names the pair of centres that float32 cannot tell apart."""
+    f = np.asarray(centres, dtype=np.float64).ravel()
+    if f.size < 2:
+        raise ValueError("squeeze_edges() needs at least 2 centre frequencies (a cell is the distance between neighbours), not %d" % f.size)
+    if f.size > _lib.SQUEEZE_MAX_CELLS:
+        raise ValueError("squeeze_edges() takes at most %d centre frequencies, not %d" % (_lib.SQUEEZE_MAX_CELLS, f.size))
+    if not np.all(np.isfinite(f)) or np.any(f <= 0):
+        raise ValueError("the centre frequencies must be finite and positive")
+    step = np.diff(f)
+    if not (np.all(step > 0) or np.all(step < 0)):
+        raise ValueError("the centre frequencies must be strictly monotonic")
+    descending = bool(f[0] > f[-1])
+    ln = np.log(f[::-1] if descending else f)
+    with np.errstate(over="ignore"):
+        edges = np.exp(np.concatenate(([ln[0] - 0.5 * (ln[1] - ln[0])], 0.5 * (ln[:-1] + ln[1:]),
+                                       [ln[-1] + 0.5 * (ln[-1] - ln[-2])]))).astype(np.float32)
+    if not np.all(np.isfinite(edges)) or edges[0] <= 0:
+        raise ValueError("the cells around the centre frequencies %g .. %g Hz leave float32's range" % (f.min(), f.max()))
+    flat = np.flatnonzero(np.diff(edges) <= 0)
+    if flat.size:
+        # edges k and k + 1 enclose the ascending centre k: it lies too close to a neighbour
+        k = min(int(flat[0]), f.size - 2)
+        a, b = (f.size - 1 - k, f.size - 2 - k) if descending else (k, k + 1)
+        raise ValueError("the centres %d and %d (%.17g and %.17g Hz) are too close: the edges of the cell between them are "
+                         "the same float32" % (min(a, b), max(a, b), f[min(a, b)], f[max(a, b)]))
+    return edges, descending
+
+
+_SQUEEZE_OUTPUTS = (("coefficients", np.complex64), ("power", np.float32), ("frequency", np.float32), ("index", np.int32))
+
+
+class SqueezeResult(_RowOpResult):
+    """What squeeze() left on the device, rows ``pitch`` elements apart in one DeviceBuffer and only those of ``outputs``:
+    ``coefficients`` complex64 and ``power`` float32, each (C, L, N) over the L cells; ``frequency`` float32 and ``index``
+    int32, each (C, R, N) over the R input rows ``rows`` = (first, count).  ``to_host()`` brings them over; until
+    ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr + _offsets()[name]``."""
+
+    def __init__(self, buffer, n_channels, rows, n_cells, n_cols, pitch, outputs):
+        self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), tuple(rows), tuple(outputs)
+        self.n_channels, self.n_rows, self.n_cells, self.n_cols = int(n_channels), int(rows[1]), int(n_cells), int(n_cols)
+
+    def _planes(self):
+        lead = {"coefficients": (self.n_channels, self.n_cells), "power": (self.n_channels, self.n_cells),
+                "frequency": (self.n_channels, self.n_rows), "index": (self.n_channels, self.n_rows)}
+        return tuple((name, dtype, lead[name]) for name, dtype in _SQUEEZE_OUTPUTS if name in self.outputs), self.n_cols
+
+
+def _squeeze_outputs(outputs):
+    names = [name for name, _ in _SQUEEZE_OUTPUTS]
+    seq = (outputs,) if isinstance(outputs, str) else outputs
+    try:
+        ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("'outputs' must name at least one of %s, each once, not %r" % (", ".join(names), outputs))
+    return tuple(seq)
+
+
+def _squeeze_cells(edges):
+    arr = np.asarray(edges)
+    if arr.ndim != 1 or arr.size < 2 or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'edges' must hold the L + 1 real edges of L >= 1 cells, not %s of shape %r" % (arr.dtype, arr.shape))
+    if arr.size - 1 > _lib.SQUEEZE_MAX_CELLS:
+        raise ValueError("'edges' holds %d cells, more than the %d that squeeze() takes" % (arr.size - 1, _lib.SQUEEZE_MAX_CELLS))
+    with np.errstate(over="ignore"):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if not np.all(np.isfinite(arr)) or np.any(arr <= 0):
+        raise ValueError("'edges' must be finite and above 0")
+    flat = np.flatnonzero(np.diff(arr) <= 0)
+    if flat.size:
+        raise ValueError("'edges' must be strictly ascending as float32: edges[%d] = %.9g is not above edges[%d] = %.9g"
+                         % (flat[0] + 1, arr[flat[0] + 1], flat[0], arr[flat[0]]))
+    return arr
+
+
+def squeeze(result, rows, g, floor2, nu, hz_per_cycle, segments, edges, descending=False, outputs=("coefficients",)):
+    """The synchrosqueezed transform of a run of rows of a complex DeviceResult, computed where the result lies
+    (gcwt_squeeze; include/ghostcwt.h has the definition): every coefficient of the rows ``rows`` = (first, count) goes to
+    the cell of ``edges`` -- (L + 1,) float32, > 0, strictly ascending, as squeeze_edges returns them -- that holds its own
+    instantaneous ``frequency`` (ridge()'s, on every row), and what lands in a cell is added, weighted with ``g``, in
+    ascending row order.  ``g``: (S,) finite weights as band_weights returns them; ``floor2``: (S,) >= 0, an entry whose
+    |w|^2 is not above it stays out; ``nu``, ``hz_per_cycle``, ``segments``: exactly ridge()'s.  ``descending``: cell l is
+    output row L - 1 - l.  ``index`` is the output row of every entry, -1 where it is out.  Only the planes of ``outputs``
+    are allocated.  The result itself is only read.  -> SqueezeResult, which stays on the device until ``to_host()`` /
+    ``free()``."""
+    c, s, n = _resident_complex(result, "squeeze", "a result sharded over several GPUs is not supported")
+    outputs = _squeeze_outputs(outputs)
+    first, count = _row_range(rows, s, "rows")
+    g = _band_weight(g, s, "g", False)
+    floor2 = _ridge_table(floor2, s, "floor2", False)
+    nu = _ridge_table(nu, s, "nu", False)
+    if isinstance(hz_per_cycle, (bool, np.bool_)) or not isinstance(hz_per_cycle, (int, float, np.integer, np.floating)):
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    with np.errstate(over="ignore"):
+        hz = np.float32(hz_per_cycle)
+    if not np.isfinite(hz) or not hz > 0:
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    seg = _ridge_segments(segments, n)
+    edges = _squeeze_cells(edges)
+    if not isinstance(descending, (bool, np.bool_)):
+        raise ValueError("'descending' must be True or False, not %r" % (descending,))
+    f32p = C.POINTER(C.c_float)
+    res = SqueezeResult(None, c, (first, count), edges.size - 1, n, _pitch(n), outputs)
+    return _run_into(
+        res, "squeeze", "%d channels, %d cells, %d rows, %d columns, %s" % (c, edges.size - 1, count, n, " + ".join(outputs)),
+        "fewer cells, fewer outputs or an output_stride",
+        lambda ptr: check(lib.gcwt_squeeze(result.buffer.ptr, result.pitch, c, s, n, first, count, g.ctypes.data_as(f32p),
+                                           floor2.ctypes.data_as(f32p), nu.ctypes.data_as(f32p), float(hz),
+                                           seg.ctypes.data_as(C.POINTER(C.c_int64)), len(seg), edges.ctypes.data_as(f32p),
+                                           edges.size - 1, int(bool(descending)), ptr.get("coefficients"), ptr.get("power"),
+                                           ptr.get("frequency"), ptr.get("index"), res.pitch)))
+
+
 def _traces(buffer_ptr, pitch, n_traces, n_cols, what):
     """(pointer, pitch, n_traces, n_cols) of float32 traces on the device as the C entries take them."""
     ptr = buffer_ptr if isinstance(buffer_ptr, C.c_void_p) else C.c_void_p(buffer_ptr)

@@ -87,6 +87,15 @@ class _Ridge:
         return out
 
 
+class _Squeeze:
+    """What ContinuousWaveletTransform.squeeze returns (host arrays)."""
+
+    def __init__(self, coefficients, power, frequency, index, bin_frequencies, edges, rows, frequencies, time, min_amplitude):
+        self.coefficients, self.power, self.frequency, self.index = coefficients, power, frequency, index
+        self.bin_frequencies, self.edges, self.rows, self.frequencies = bin_frequencies, edges, rows, frequencies
+        self.time, self.min_amplitude = time, min_amplitude
+
+
 class _Events:
     """What ContinuousWaveletTransform.detect returns (host arrays)."""
 
@@ -658,6 +667,81 @@ class ContinuousWaveletTransform(WaveletTransform):
         return _Ridge(out.get("row"), out.get("amplitude"), out.get("frequency"), out.get("offset"),
                       np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
                       [f[a:a + n] for a, n in rows], t, f)
+
+    def squeeze(self, bins=None, *, freq_limits=None, min_amplitude=0.0, outputs=("coefficients",)):
+        """The synchrosqueezed transform of the last transform -- a drifting theta, the chirp inside a ripple or two
+        nearby rhythms, sharp in frequency where the rows themselves are an octave wide --, made on the device: every
+        coefficient is moved to the frequency cell that its own phase advance names, and what lands in a cell is
+        added.  The transform must have been ``output='complex'`` on one device.  ``freq_limits=(lo, hi)``: only the
+        rows whose frequency lies in the closed interval are squeezed (default: all rows).  ``bins``: the cells, by
+        their centre frequencies: None -- the selected rows' own frequencies (at least 2 rows); an int L >= 2 --
+        ``np.geomspace`` between the selected rows' first and last frequency, in the rows' order; an array -- the
+        centres themselves, positive and strictly monotonic, at least 2.  The cells' edges are the geometric midpoints
+        between neighbouring centres, the outer two half a step beyond (engine.squeeze_edges).  ``min_amplitude``: an
+        entry stays out unless its amplitude, in ``ridge().amplitude``'s units (a sinusoid of amplitude A on a row's
+        frequency reads A), is above it.  ``outputs``: which of 'coefficients', 'power', 'frequency', 'index' to
+        compute.  With w_r the coefficient of row r at a column, g = engine.band_weights(frequencies, wavelet)[0] and
+        R selected rows, the returned object has ``frequency`` (C, R, N) float32, Hz: ``ridge()``'s instantaneous
+        frequency on every row -- the phase advance from the column before to the column after inside the column's
+        own epoch, unwrapped against the row's own frequency, so that an output stride does not alias it; NaN in a gap
+        and in an epoch of one column; ``index`` (C, R, N) int32: the cell, as an index into ``bin_frequencies``,
+        that the entry was added to, -1 where it stays out: below ``min_amplitude``, no frequency, or a frequency
+        outside the cells; ``coefficients`` (C, L, N) complex64: per cell the sum of g_r w_r over its entries, the rows
+        in ascending order (one chain of float32 fused multiply-adds per cell and column, ``bandpass()``'s arithmetic:
+        the sum over the cells of a column is the analytic signal of the entries that are in); ``power`` (C, L, N)
+        float32 = |coefficients|^2.  Those not asked for are None.  Also ``bin_frequencies`` (L,) float64,
+        ``edges`` (L + 1,) float32 ascending, ``rows`` = (first, count), ``frequencies`` (R,), ``time`` (N,) and
+        ``min_amplitude``.  After the reference's single-channel call the channel axis is dropped.  Columns in a gap
+        between epochs are exactly 0 with ``index`` -1.  Everything but the arctangent is prescribed single float32
+        operations (include/ghostcwt.h: gcwt_squeeze), without atomics: two runs agree in bits, whichever outputs are
+        asked for.  What it does not do: there is no second-order (chirp-rate) correction, so a fast chirp is as
+        sharp as its frequency changes little over one wavelet; weak entries carry noise phases and go where those
+        say, so on real recordings ``min_amplitude`` is not optional; and the output is as large as the rows it came
+        from -- L cells of N columns -- and crosses to the host: fewer cells, fewer outputs or an ``output_stride``
+        keep it small.  The resident result, ``fetch()`` and the result attributes are untouched."""
+        from .. import engine
+        result, squeeze = self._resident_rows("squeeze")
+        f = np.array(self._frequencies)
+        rows = (0, f.size) if freq_limits is None else engine.coupling_rows(freq_limits, f, "freq_limits")
+        own = f[rows[0]:rows[0] + rows[1]]
+        if isinstance(min_amplitude, (bool, np.bool_)) or not isinstance(min_amplitude, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(min_amplitude)) or float(min_amplitude) < 0:
+            raise ValueError("squeeze(): 'min_amplitude' must be a finite number, at least 0, not %r" % (min_amplitude,))
+        if bins is None or (isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_))):
+            if own.size < 2:
+                raise ValueError("squeeze(): bins=%r needs at least 2 selected rows to take the cells from, not %d"
+                                 % (bins, own.size))
+            if bins is not None and int(bins) < 2:
+                raise ValueError("squeeze(): 'bins' must be None, an int >= 2 or an array of centre frequencies, not %r" % (bins,))
+            centres = own.astype(np.float64) if bins is None else np.geomspace(own[0], own[-1], int(bins))
+        else:
+            try:
+                centres = np.asarray(bins, dtype=np.float64).ravel()
+                ok = np.ndim(bins) == 1 and not isinstance(bins, (str, bytes)) and np.asarray(bins).dtype != np.bool_
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("squeeze(): 'bins' must be None, an int >= 2 or an array of centre frequencies, not %r" % (bins,))
+        edges, descending = engine.squeeze_edges(centres)
+        e = engine.ridge_weights(f, self._wavelet).astype(np.float64)
+        with np.errstate(over="ignore"):
+            floor2 = (np.square(np.float64(min_amplitude)) / e).astype(np.float32)
+        if not np.all(np.isfinite(floor2)):
+            raise ValueError("squeeze(): 'min_amplitude' = %r squared leaves float32's range" % (min_amplitude,))
+        stride, fs = self._stride, float(self._fs)
+        t = self.time
+        t = None if t is None else np.asarray(t)
+        segments = engine.segments_of(t, stride / fs, fs, result.shape[2])
+        res = engine.squeeze(result, rows, engine.band_weights(f, self._wavelet)[0], floor2, 2 * np.pi * f * stride / fs,
+                             fs / stride, segments, edges, descending, outputs)
+        try:
+            out = res.to_host()
+        finally:
+            res.free()
+        if squeeze:
+            out = {k: v[0] for k, v in out.items()}
+        return _Squeeze(out.get("coefficients"), out.get("power"), out.get("frequency"), out.get("index"), centres, edges,
+                        (int(rows[0]), int(rows[1])), own, t, float(min_amplitude))
 
     def detect(self, band, *, on="envelope", threshold=3.0, edge=0.0, units="sd", min_duration=0.0, max_duration=None,
                min_gap=0.0, stats="mean", baseline=None, smooth=None, combine=False):

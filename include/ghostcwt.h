@@ -364,6 +364,44 @@ int gcwt_ridge(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n
                const int32_t* bands, int32_t n_bands, const float* e, const float* nu, float hz_per_cycle,
                const int64_t* segments, int64_t n_segments,
                int32_t* d_row, float* d_amplitude, float* d_offset, float* d_frequency, int64_t out_pitch);
+/* The synchrosqueezed transform of a run of rows of a device-resident complex result, on the device that holds the rows
+ * (csrc/squeeze.hip): every coefficient is moved to the frequency cell that its own phase advance names, and what lands
+ * in a cell is added.  d_rows, pitch and n_cols are those of gcwt_coherence.  The input rows are row_first .. row_first +
+ * n_rows - 1 = R rows inside [0, n_scales).  g, floor2, nu: n_scales float32 each in HOST memory: g any finite weight
+ * (ghost_amd.engine.band_weights' g makes the sum over the cells of a column the band's analytic signal), floor2 finite
+ * and >= 0, a threshold on |w|^2, nu finite and >= 0 as for gcwt_ridge.  hz_per_cycle, segments and n_segments are
+ * exactly gcwt_ridge's.  edges: n_cells + 1 float32 in HOST memory, finite, > 0 and strictly ascending, 1 <= n_cells = L <=
+ * GCWT_SQUEEZE_MAX_CELLS: cell l holds the frequencies edges[l] <= f < edges[l + 1] (ghost_amd.engine.squeeze_edges makes
+ * them from centre frequencies).  The entry copies the tables to the device and frees the copy.  For every channel c,
+ * input row r and column t, with w = W[c][r][t], every operation a single correctly rounded float32 one and no product
+ * contracted into a sum that is not written as fmaf:
+ *   d_frequency [C][R][n_cols]      float32    Hz: gcwt_ridge's frequency with row = r -- tm, tp, span, a = W[c][r][tp], b =
+ *     W[c][r][tm], re, im, dphi, k, num, scale, frequency = num * scale, operation for operation.  NaN where span == 0 and
+ *     where re and im are both 0.  It does not depend on floor2.
+ *   cell: the largest l with edges[l] <= frequency, found by binary search on the float32 values.  The entry is out where
+ *     !(fmaf(w.im, w.im, w.re * w.re) > floor2[r]), where frequency is NaN, where frequency < edges[0] and where frequency
+ *     >= edges[L].
+ *   d_index [C][R][n_cols]          int32      the output row the entry was added to: l, or L - 1 - l with descending != 0;
+ *     -1 where the entry is out
+ *   d_coefficients [C][L][n_cols]   complex64  (x, y): from (0, 0), the input rows walked in ascending r, every entry
+ *     that is not out does on its output row   x = fmaf(g[r], w.re, x)   y = fmaf(g[r], w.im, y)   -- one chain per cell
+ *     and column: gcwt_bandpass's arithmetic, and with one cell that holds every entry its analytic
+ *   d_power [C][L][n_cols]          float32    fmaf(y, y, x * x)
+ * Columns in a gap between epochs (exact zeros) give exact zeros, index -1 and frequency NaN.  Nothing depends on the
+ * column count, the pitch, the tiling, the grouping of the cells or which outputs are asked for, and two runs agree in
+ * bits; there are no atomics.  The sum over the cells of a column is the sum of g[r] w over the entries that are not out:
+ * the result stays invertible.  There is no second-order (chirp-rate) correction; an entry below the noise carries a
+ * noise phase and goes where that says: floor2 is what keeps it out.  Any output may be NULL, but not all; their rows
+ * are out_pitch (>= n_cols) elements apart.  Without d_coefficients and d_power nothing is summed.  A workgroup takes
+ * GCWT_SQUEEZE_TILE_COLS columns, counted from column 0, of GCWT_SQUEEZE_GROUP_CELLS consecutive output rows, counted
+ * from row 0, and walks all R input rows: more cells than one group holds cost another walk.  Plan-independent; the
+ * device is the one that holds d_rows.  Arguments -- every table entry, edge and segment among them -- are checked before
+ * any device call (GCWT_ERR_INVALID; the message names the first offending index). */
+enum { GCWT_SQUEEZE_TILE_COLS = 512, GCWT_SQUEEZE_GROUP_CELLS = 16, GCWT_SQUEEZE_MAX_CELLS = 4096 };
+int gcwt_squeeze(const float* d_rows, int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n_cols,
+                 int32_t row_first, int32_t n_rows, const float* g, const float* floor2, const float* nu, float hz_per_cycle,
+                 const int64_t* segments, int64_t n_segments, const float* edges, int32_t n_cells, int32_t descending,
+                 float* d_coefficients, float* d_power, float* d_frequency, int32_t* d_index, int64_t out_pitch);
 /* The steps of threshold-crossing detection on float32 traces that lie on a device (csrc/detect_runs.hip): n_traces
  * rows of n_cols (1 .. 2^40 - 1) live columns, pitch (>= n_cols) elements apart -- what gcwt_bandpass leaves in
  * d_envelope / d_power with n_traces = C * n_bands, or any row of an amplitude result.  All are plan-independent and
