@@ -3,9 +3,7 @@
 // Plan-independent, like gcwt_triggered.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
-#include <vector>
 
 #include "../../include/ghostcwt_debug.h"
 #include "bandpass.h"
@@ -23,23 +21,9 @@ constexpr const char* kOp = "gcwt_bandpass";
 
 // the grid of (n_channels, n_cols, n_bands), each already checked
 int cut(int32_t n_channels, int64_t n_cols, int32_t n_bands, gcwt::BpArgs* a) {
-  a->n_channels = n_channels; a->n_cols = n_cols; a->n_bands = n_bands;
-  a->n_ctiles = (n_cols - 1) / gcwt::kBpCols + 1;
-  a->n_groups = (n_bands - 1) / gcwt::kBpBands + 1;
-  // (each factor is below 2^31 before it is multiplied)
-  if (a->n_ctiles > 0x7fffffff || (a->n_units = a->n_ctiles * n_channels) > 0x7fffffff ||
-      gcwt::bandpass_blocks(*a) > 0x7fffffff)
-    return fail(GCWT_ERR_INVALID, "gcwt_bandpass: channels x columns x bands need more than 2^31 - 1 workgroups: fewer bands or "
-                                  "fewer channels per call");
-  return GCWT_OK;
-}
-
-int check_weights(const char* name, const float* w, int32_t n_scales, bool sign) {
-  for (int32_t r = 0; r < n_scales; ++r)
-    if (!std::isfinite(w[r]) || (sign && w[r] < 0.f))
-      return fail(GCWT_ERR_INVALID, std::string("gcwt_bandpass: ") + name + "[" + std::to_string(r) + "] must be finite" +
-                                        (sign ? " and at least 0" : ""));
-  return GCWT_OK;
+  a->n_bands = n_bands;
+  return cut_column_tiles(kOp, "bands", gcwt::kBpCols, gcwt::bandpass_blocks, n_channels, n_cols,
+                          (n_bands - 1) / gcwt::kBpBands + 1, a);
 }
 
 // everything that needs no device; fills the grid's numbers
@@ -47,20 +31,13 @@ int check_and_cut(int64_t pitch, int32_t n_channels, int32_t n_scales, int64_t n
                   const float* g, const float* h, gcwt::BpArgs* a) {
   int rc = check_channels(kOp, n_channels);
   if (!rc) rc = check_rows(kOp, n_scales, n_cols, pitch);
-  if (rc) return rc;
-  if (n_bands < 1) return fail(GCWT_ERR_INVALID, "gcwt_bandpass: n_bands must be at least 1");
-  for (int32_t k = 0; k < n_bands; ++k) {
-    rc = check_row_range(kOp, ("band " + std::to_string(k)).c_str(), bands[2 * k], bands[2 * k + 1], n_scales);
-    if (rc) return rc;
-  }
-  if (g) rc = check_weights("g", g, n_scales, false);
-  if (!rc && h) rc = check_weights("h", h, n_scales, true);
+  if (!rc) rc = check_band_list(kOp, bands, n_bands, n_scales);
+  if (!rc && g) rc = check_table(kOp, "g", g, n_scales, Bound::kNone);
+  if (!rc && h) rc = check_table(kOp, "h", h, n_scales, Bound::kAtLeast0);
   if (rc) return rc;
   a->pitch = pitch; a->n_scales = n_scales;
   return cut(n_channels, n_cols, n_bands, a);
 }
-
-bool on16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 
@@ -100,28 +77,21 @@ int gcwt_bandpass(const float* d_rows, int64_t pitch, int32_t n_channels, int32_
     if (rc) return rc;
 
     // one copy: the band table, then g, then h (zeros for a weight array that no output asked for needs)
-    const size_t table = (size_t)n_bands * 2 * sizeof(int32_t), weights = (size_t)n_scales * sizeof(float);
-    const std::vector<float> none((size_t)n_scales, 0.f);
-    DeviceCopy copy;
-    hipError_t e = copy.alloc(table + 2 * weights);
-    if (e != hipSuccess)
-      return fail(GCWT_ERR_NOMEM, std::string("gcwt_bandpass: no device memory for the band table: ") + hipGetErrorString(e));
-    e = copy.put(0, bands, table);
-    if (e == hipSuccess) e = copy.put(table, g ? g : none.data(), weights);
-    if (e == hipSuccess) e = copy.put(table + weights, h ? h : none.data(), weights);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_bandpass: ") + hipGetErrorString(e));
+    const size_t weights = (size_t)n_scales * sizeof(float);
+    DeviceTable tab;
+    const size_t at_bands = tab.add(bands, (size_t)n_bands * 2 * sizeof(int32_t)), at_g = tab.add(g, weights);
+    const size_t at_h = tab.add(h, weights);
+    rc = tab.upload(kOp, "the band table");
+    if (rc) return rc;
 
     a.rows = reinterpret_cast<const float2*>(d_rows);
-    a.bands = static_cast<const int2*>(copy.p);
-    a.g = reinterpret_cast<const float*>(static_cast<const char*>(copy.p) + table);
-    a.h = a.g + n_scales;
+    a.bands = tab.at<int2>(at_bands);
+    a.g = tab.at<float>(at_g);
+    a.h = tab.at<float>(at_h);
     a.out_pitch = out_pitch;
     a.analytic = reinterpret_cast<float2*>(d_analytic); a.envelope = d_envelope; a.power = d_power;
-    a.aligned = pitch % 2 == 0 && out_pitch % 2 == 0 && on16(d_rows) && on16(d_analytic) && on16(d_envelope) && on16(d_power);
-    e = gcwt::launch_bandpass(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_bandpass: ") + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    a.aligned = rows_on16(d_rows, pitch, out_pitch, {d_analytic, d_envelope, d_power});
+    return finish(kOp, gcwt::launch_bandpass(a, nullptr));
   });
 }
 

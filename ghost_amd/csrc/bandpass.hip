@@ -34,13 +34,6 @@ constexpr int kBpDepth = 4;                                 // rows whose loads 
 
 struct Acc { float re, im, p; };
 
-// The band table and the weights are written by the host before the launch and by nobody after it: read through the
-// constant address space, a wave-uniform index gives a scalar load.
-template <class T>
-using Const = const T __attribute__((address_space(4)))*;
-template <class T>
-__device__ __forceinline__ Const<T> constant(const T* p) { return (Const<T>)reinterpret_cast<uintptr_t>(p); }
-
 // one row enters the chains of one column: the prescribed sequence
 __device__ __forceinline__ void add_row(Acc& s, float g, float h, float2 w, float r2) {
   s.re = fmaf(g, w.x, s.re);

@@ -145,27 +145,23 @@ int gcwt_coherence(const float* d_rows, int64_t pitch, int32_t n_channels, int32
     auto runs = [&] { return (n_bins + run_bins - 1) / run_bins; };
     while ((int64_t)tasks.size() * runs() * n_scales > 0x7fffffff) run_bins *= 2;
 
-    const size_t task_bytes = sizeof(gcwt::CohTask) * tasks.size();
-    const size_t ent_bytes = sizeof(gcwt::CohEntry) * std::max<size_t>(1, ent.size());
-    DeviceCopy tab;
-    hipError_t e = tab.alloc(task_bytes + ent_bytes);
-    if (e != hipSuccess) return fail(GCWT_ERR_NOMEM, std::string("gcwt_coherence: ") + hipGetErrorString(e));
-    e = tab.put(0, tasks.data(), task_bytes);
-    if (e == hipSuccess && !ent.empty()) e = tab.put(task_bytes, ent.data(), sizeof(gcwt::CohEntry) * ent.size());
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coherence: ") + hipGetErrorString(e));
+    // one copy: the tasks, then their entries (one of zeros where there is none)
+    if (ent.empty()) ent.push_back(gcwt::CohEntry{});
+    DeviceTable tab;
+    const size_t at_tasks = tab.add(tasks.data(), sizeof(gcwt::CohTask) * tasks.size());
+    const size_t at_entries = tab.add(ent.data(), sizeof(gcwt::CohEntry) * ent.size());
+    rc = tab.upload(kOp, nullptr);
+    if (rc) return rc;
 
     gcwt::CohArgs a{};
     a.rows = reinterpret_cast<const float2*>(d_rows);
     a.pitch = pitch; a.n_cols = n_cols; a.window = window; a.n_bins = n_bins; a.out_pitch = out_pitch;
     a.n_channels = n_channels; a.n_scales = n_scales; a.n_tasks = (int32_t)tasks.size();
     a.run_bins = run_bins; a.n_runs = runs();
-    a.tasks = static_cast<const gcwt::CohTask*>(tab.p);
-    a.entries = reinterpret_cast<const gcwt::CohEntry*>((char*)tab.p + task_bytes);
+    a.tasks = tab.at<gcwt::CohTask>(at_tasks);
+    a.entries = tab.at<gcwt::CohEntry>(at_entries);
     a.power = d_power; a.cross = reinterpret_cast<float2*>(d_cross); a.coherence = d_coherence;
-    e = gcwt::launch_coherence(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coherence: ") + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    return finish(kOp, gcwt::launch_coherence(a, nullptr));
   });
 }
 

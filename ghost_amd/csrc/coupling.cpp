@@ -83,10 +83,7 @@ int gcwt_coupling(const float* d_rows, int64_t pitch, int32_t n_channels, int32_
     a.rows = reinterpret_cast<const float2*>(d_rows);
     a.out_pitch = out_pitch;
     a.vector = reinterpret_cast<float2*>(d_vector); a.mvl = d_mvl; a.amplitude = d_amplitude;
-    hipError_t e = gcwt::launch_coupling(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coupling: ") + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    return finish(kOp, gcwt::launch_coupling(a, nullptr));
   });
 }
 

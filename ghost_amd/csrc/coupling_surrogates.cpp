@@ -97,23 +97,17 @@ int gcwt_coupling_surrogates(const float* d_rows, int64_t pitch, int32_t n_chann
     rc = resolve_device(kOp, d_rows, {d_mean, d_sd, d_count_ge, d_surrogates});
     if (rc) return rc;
 
-    DeviceCopy tb;
-    const size_t bytes = table.size() * sizeof(int32_t);
-    hipError_t e = tb.alloc(bytes);
-    if (e != hipSuccess)
-      return fail(GCWT_ERR_NOMEM, std::string("gcwt_coupling_surrogates: no device memory for the shift list: ") + hipGetErrorString(e));
-    e = tb.put(0, table.data(), bytes);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coupling_surrogates: ") + hipGetErrorString(e));
+    DeviceTable tab;
+    const size_t at_shifts = tab.add(table.data(), table.size() * sizeof(int32_t));
+    rc = tab.upload(kOp, "the shift list");
+    if (rc) return rc;
 
     a.rows = reinterpret_cast<const float2*>(d_rows);
-    a.shifts = static_cast<const int32_t*>(tb.p);
+    a.shifts = tab.at<int32_t>(at_shifts);
     a.n_shifts = n_shifts;
     a.out_pitch = out_pitch;
     a.mean = d_mean; a.sd = d_sd; a.count_ge = d_count_ge; a.surrogates = d_surrogates;
-    e = gcwt::launch_coupling_surrogates(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_coupling_surrogates: ") + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    return finish(kOp, gcwt::launch_coupling_surrogates(a, nullptr));
   });
 }
 

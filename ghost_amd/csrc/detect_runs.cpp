@@ -34,14 +34,6 @@ int check_and_cut(const std::string& op, const float* d_trace, int64_t pitch, in
 
 }  // namespace gcwt
 
-namespace {
-
-int hip_failed(const std::string& op, hipError_t e) { return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e)); }
-
-size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-}  // namespace
-
 extern "C" {
 
 int gcwt_trace_stats(const float* d_trace, int64_t pitch, int64_t n_traces, int64_t n_cols, int64_t* n, double* mean,
@@ -65,7 +57,7 @@ int gcwt_trace_stats(const float* d_trace, int64_t pitch, int64_t n_traces, int6
     e = launch_trace_stats(a, d_tiles, d_traces, nullptr);
     std::vector<TileSums> sums((size_t)n_traces);
     if (e == hipSuccess) e = hipMemcpy(sums.data(), d_traces, traces, hipMemcpyDeviceToHost);      // (waits for the kernels)
-    if (e != hipSuccess) return hip_failed(op, e);
+    if (e != hipSuccess) return hip_failed(op.c_str(), e);
     for (int64_t i = 0; i < n_traces; ++i) {
       const TileSums& s = sums[(size_t)i];
       n[i] = s.n;
@@ -88,8 +80,8 @@ int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64
     if (rc) return rc;
     if (!lo) return fail(GCWT_ERR_INVALID, op + ": lo is NULL");
     if (!counts) return fail(GCWT_ERR_INVALID, op + ": counts is NULL");
-    for (int64_t i = 0; i < n_traces; ++i)
-      if (!std::isfinite(lo[i])) return fail(GCWT_ERR_INVALID, op + ": lo[" + std::to_string(i) + "] must be finite");
+    rc = check_table(op.c_str(), "lo", lo, n_traces, Bound::kNone);
+    if (rc) return rc;
     if (capacity < 0) return fail(GCWT_ERR_INVALID, op + ": capacity must be at least 0");
     if (capacity > 0 && (!d_start || !d_stop || !d_peak_col || !d_peak))
       return fail(GCWT_ERR_INVALID, op + ": capacity is above 0 and d_start, d_stop, d_peak_col or d_peak is NULL");
@@ -105,7 +97,7 @@ int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64
     hipError_t e = work.alloc(at_lo + (size_t)n_traces * sizeof(float));
     if (e != hipSuccess) return fail(GCWT_ERR_NOMEM, op + ": no device memory for the tiles' counts: " + hipGetErrorString(e));
     e = work.put(at_lo, lo, (size_t)n_traces * sizeof(float));
-    if (e != hipSuccess) return hip_failed(op, e);
+    if (e != hipSuccess) return hip_failed(op.c_str(), e);
     char* base = static_cast<char*>(work.p);
     a.counts = reinterpret_cast<int2*>(base);
     a.offsets = reinterpret_cast<longlong2*>(base + at_offsets);
@@ -118,15 +110,12 @@ int gcwt_trace_runs(const float* d_trace, int64_t pitch, int64_t n_traces, int64
     e = launch_run_count(a, nullptr);
     std::vector<long long> first((size_t)n_traces + 1);
     if (e == hipSuccess) e = hipMemcpy(first.data(), a.trace_first, first_bytes, hipMemcpyDeviceToHost);   // (waits)
-    if (e != hipSuccess) return hip_failed(op, e);
+    if (e != hipSuccess) return hip_failed(op.c_str(), e);
     for (int64_t i = 0; i < n_traces; ++i) counts[i] = first[(size_t)i + 1] - first[(size_t)i];
     const int64_t n_runs = first[(size_t)n_traces];
     if (n_runs == 0 || n_runs > capacity) return (int)GCWT_OK;                  // nothing to write / the caller sizes and returns
 
-    e = launch_run_fill(a, n_runs, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return hip_failed(op, e);
-    return (int)GCWT_OK;
+    return finish(op.c_str(), launch_run_fill(a, n_runs, nullptr));
   });
 }
 

@@ -54,13 +54,6 @@ constexpr int kRgDepth = 4;                                 // rows whose loads 
 
 struct Best { float q, qm, qp; int row; };
 
-// The tables are written by the host before the launch and by nobody after it: read through the constant address
-// space, a wave-uniform index gives a scalar load.
-template <class T>
-using Const = const T __attribute__((address_space(4)))*;
-template <class T>
-__device__ __forceinline__ Const<T> constant(const T* p) { return (Const<T>)reinterpret_cast<uintptr_t>(p); }
-
 // row r enters the ranking of one (band, column); q_below: the q of row r - 1 at this column
 __device__ __forceinline__ void rank_row(Best& s, int r, float q, float q_below) {
   if (s.row == r - 1) s.qp = q;        // (before any winner row is -1: at r = 0 this sets a qp that nothing reads)

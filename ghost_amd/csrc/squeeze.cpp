@@ -20,17 +20,6 @@ namespace {
 
 constexpr const char* kOp = "gcwt_squeeze";
 
-// the grid of (n_channels, n_cols, n_groups), each already checked
-int cut(int32_t n_channels, int64_t n_cols, int32_t n_groups, gcwt::SqArgs* a) {
-  a->n_channels = n_channels; a->n_cols = n_cols; a->n_groups = n_groups;
-  a->n_ctiles = (n_cols - 1) / gcwt::kSqCols + 1;
-  // (each factor is below 2^31 before it is multiplied)
-  if (a->n_ctiles > 0x7fffffff || (a->n_units = a->n_ctiles * n_channels) > 0x7fffffff || gcwt::squeeze_blocks(*a) > 0x7fffffff)
-    return fail(GCWT_ERR_INVALID, "gcwt_squeeze: channels x columns x cells need more than 2^31 - 1 workgroups: fewer cells or "
-                                  "fewer channels per call");
-  return GCWT_OK;
-}
-
 // finite, above 0, strictly ascending
 int check_edges(const float* edges, int32_t n_cells) {
   for (int32_t l = 0; l <= n_cells; ++l) {
@@ -42,9 +31,6 @@ int check_edges(const float* edges, int32_t n_cells) {
   }
   return GCWT_OK;
 }
-
-bool on16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 }  // namespace
 
@@ -66,15 +52,10 @@ extern "C" int gcwt_squeeze(const float* d_rows, int64_t pitch, int32_t n_channe
     int rc = check_channels(kOp, n_channels);
     if (!rc) rc = check_rows(kOp, n_scales, n_cols, pitch);
     if (!rc) rc = check_row_range(kOp, "rows", row_first, n_rows, n_scales);
-    if (rc) return rc;
-    for (int32_t r = 0; r < n_scales; ++r)
-      if (!std::isfinite(g[r])) return fail(GCWT_ERR_INVALID, "gcwt_squeeze: g[" + std::to_string(r) + "] must be finite");
-    rc = check_table(kOp, "floor2", floor2, n_scales, false);
-    if (!rc) rc = check_table(kOp, "nu", nu, n_scales, false);
-    if (rc) return rc;
-    if (!std::isfinite(hz_per_cycle) || !(hz_per_cycle > 0.f)) return fail(GCWT_ERR_INVALID, "gcwt_squeeze: hz_per_cycle must be finite and above 0");
-    if (n_segments > n_cols) return fail(GCWT_ERR_INVALID, "gcwt_squeeze: more segments than columns");
-    rc = check_segments(kOp, segments, n_segments, n_cols);
+    if (!rc) rc = check_table(kOp, "g", g, n_scales, Bound::kNone);
+    if (!rc) rc = check_table(kOp, "floor2", floor2, n_scales, Bound::kAtLeast0);
+    if (!rc) rc = check_table(kOp, "nu", nu, n_scales, Bound::kAtLeast0);
+    if (!rc) rc = check_phase_advance(kOp, hz_per_cycle, segments, n_segments, n_cols);
     if (rc) return rc;
     if (n_cells < 1 || n_cells > gcwt::kSqMaxCells)
       return fail(GCWT_ERR_INVALID, "gcwt_squeeze: n_cells must be 1 .. " + std::to_string(gcwt::kSqMaxCells));
@@ -83,44 +64,35 @@ extern "C" int gcwt_squeeze(const float* d_rows, int64_t pitch, int32_t n_channe
     if (out_pitch < n_cols) return fail(GCWT_ERR_INVALID, "gcwt_squeeze: out_pitch is below n_cols");
     a.pitch = pitch; a.n_scales = n_scales; a.first = row_first; a.count = n_rows; a.n_cells = n_cells;
     // without coefficients and power nothing is summed: one group makes frequency and index
-    rc = cut(n_channels, n_cols, d_coefficients || d_power ? (n_cells - 1) / gcwt::kSqCells + 1 : 1, &a);
+    rc = cut_column_tiles(kOp, "cells", gcwt::kSqCols, gcwt::squeeze_blocks, n_channels, n_cols,
+                          d_coefficients || d_power ? (n_cells - 1) / gcwt::kSqCells + 1 : 1, &a);
     if (rc) return rc;
 
     rc = resolve_device(kOp, d_rows, {d_coefficients, d_power, d_frequency, d_index});
     if (rc) return rc;
 
     // one copy: the segment table (16-byte entries first), g, floor2, nu, the edges
-    const size_t seg_bytes = (size_t)n_segments * 2 * sizeof(int64_t), weights = (size_t)n_scales * sizeof(float);
-    const size_t at_g = seg_bytes, at_edges = up16(at_g + 3 * weights), edge_bytes = ((size_t)n_cells + 1) * sizeof(float);
-    DeviceCopy copy;
-    hipError_t err = copy.alloc(at_edges + edge_bytes);
-    if (err != hipSuccess)
-      return fail(GCWT_ERR_NOMEM, std::string("gcwt_squeeze: no device memory for the row, edge and segment tables: ") + hipGetErrorString(err));
-    err = copy.put(0, segments, seg_bytes);
-    if (err == hipSuccess) err = copy.put(at_g, g, weights);
-    if (err == hipSuccess) err = copy.put(at_g + weights, floor2, weights);
-    if (err == hipSuccess) err = copy.put(at_g + 2 * weights, nu, weights);
-    if (err == hipSuccess) err = copy.put(at_edges, edges, edge_bytes);
-    if (err != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_squeeze: ") + hipGetErrorString(err));
+    const size_t weights = (size_t)n_scales * sizeof(float);
+    DeviceTable tab;
+    const size_t at_segments = tab.add(segments, (size_t)n_segments * 2 * sizeof(int64_t));
+    const size_t at_g = tab.add(g, weights), at_floor2 = tab.add(floor2, weights), at_nu = tab.add(nu, weights);
+    const size_t at_edges = tab.add(edges, ((size_t)n_cells + 1) * sizeof(float), 16);
+    rc = tab.upload(kOp, "the row, edge and segment tables");
+    if (rc) return rc;
 
-    const char* base = static_cast<const char*>(copy.p);
     a.rows = reinterpret_cast<const float2*>(d_rows);
-    a.segments = reinterpret_cast<const longlong2*>(base);
+    a.segments = tab.at<longlong2>(at_segments);
     a.n_segments = n_segments;
-    a.g = reinterpret_cast<const float*>(base + at_g);
-    a.floor2 = a.g + n_scales;
-    a.nu = a.floor2 + n_scales;
-    a.edges = reinterpret_cast<const float*>(base + at_edges);
+    a.g = tab.at<float>(at_g);
+    a.floor2 = tab.at<float>(at_floor2);
+    a.nu = tab.at<float>(at_nu);
+    a.edges = tab.at<float>(at_edges);
     a.descending = descending != 0;
     a.hz_per_cycle = hz_per_cycle;
     a.out_pitch = out_pitch;
     a.coefficients = reinterpret_cast<float2*>(d_coefficients);
     a.power = d_power; a.frequency = d_frequency; a.index = d_index;
-    a.aligned = pitch % 2 == 0 && out_pitch % 2 == 0 && on16(d_rows) && on16(d_coefficients) && on16(d_power) &&
-                on16(d_frequency) && on16(d_index);
-    err = gcwt::launch_squeeze(a, nullptr);
-    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-    if (err != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_squeeze: ") + hipGetErrorString(err));
-    return (int)GCWT_OK;
+    a.aligned = rows_on16(d_rows, pitch, out_pitch, {d_coefficients, d_power, d_frequency, d_index});
+    return finish(kOp, gcwt::launch_squeeze(a, nullptr));
   });
 }

@@ -49,13 +49,6 @@ namespace {
 
 constexpr int kSqDepth = 4;                                 // rows whose loads are in flight
 
-// The tables are written by the host before the launch and by nobody after it: read through the constant address
-// space, a wave-uniform index gives a scalar load.
-template <class T>
-using Const = const T __attribute__((address_space(4)))*;
-template <class T>
-__device__ __forceinline__ Const<T> constant(const T* p) { return (Const<T>)reinterpret_cast<uintptr_t>(p); }
-
 // the output row of an entry with |w|^2 = r2 and frequency f, or -1 (e0 = edges[0], e_top = edges[n_cells])
 __device__ __forceinline__ int cell_row(const SqArgs& a, Const<float> edges, float e0, float e_top, bool exists, float r2,
                                         float floor2, float f) {

@@ -3,7 +3,6 @@
 // numbers that come back.  Plan-independent, like gcwt_trace_stats.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 #include <vector>
 
@@ -15,12 +14,6 @@
 static_assert(gcwt::kOrderChunkCols == GCWT_ORDER_CHUNK_COLS, "ghostcwt_debug.h names the chunk the kernels are built for");
 
 using namespace gcwt;
-
-namespace {
-
-size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-}  // namespace
 
 extern "C" {
 
@@ -39,10 +32,8 @@ int gcwt_trace_order(const float* d_trace, int64_t pitch, int64_t n_traces, int6
       return fail(GCWT_ERR_INVALID, op + ": traces x ranks need more than 2^31 - 1 workgroups: fewer traces per call");
     for (int64_t i = 0; i < n_states; ++i)
       if (ranks[i] < 0) return fail(GCWT_ERR_INVALID, op + ": ranks[" + std::to_string(i) + "] must be at least 0");
-    if (center)
-      for (int64_t i = 0; i < n_traces; ++i)
-        if (!std::isfinite(center[i])) return fail(GCWT_ERR_INVALID, op + ": center[" + std::to_string(i) + "] must be finite");
-    rc = resolve_device(op.c_str(), d_trace, {});
+    if (center) rc = check_table(op.c_str(), "center", center, n_traces, Bound::kNone);
+    if (!rc) rc = resolve_device(op.c_str(), d_trace, {});
     if (rc) return rc;
 
     a.n_ranks = n_ranks;
@@ -69,13 +60,13 @@ int gcwt_trace_order(const float* d_trace, int64_t pitch, int64_t n_traces, int6
       e = work.put(at_center, center, (size_t)n_traces * sizeof(float));
       a.center = reinterpret_cast<const float*>(base + at_center);
     }
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_failed(op.c_str(), e);
 
     e = launch_trace_order(a, nullptr);
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned) == sizeof(float), "n and out are copied as they are");
     if (e == hipSuccess) e = hipMemcpy(n, a.n, (size_t)n_traces * sizeof(long long), hipMemcpyDeviceToHost);      // (waits)
     if (e == hipSuccess) e = hipMemcpy(out, a.out, (size_t)n_states * sizeof(unsigned), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_failed(op.c_str(), e);
     return (int)GCWT_OK;
   });
 }

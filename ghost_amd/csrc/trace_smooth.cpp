@@ -2,7 +2,6 @@
 // taps, the segments and the members, the launch (trace_smooth.hip).  Plan-independent, like gcwt_trace_stats.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 #include <vector>
 
@@ -15,12 +14,6 @@ static_assert(gcwt::kSmMaxHalf == GCWT_SMOOTH_MAX_HALF, "ghostcwt.h names the li
 static_assert(gcwt::kSmCols == GCWT_SMOOTH_TILE_COLS, "ghostcwt_debug.h names the tile the kernel is built for");
 
 using namespace gcwt;
-
-namespace {
-
-size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-}  // namespace
 
 extern "C" {
 
@@ -37,8 +30,8 @@ int gcwt_trace_smooth(const float* d_trace, int64_t pitch, int64_t n_traces, int
     if (half > kSmMaxHalf)
       return fail(GCWT_ERR_INVALID, op + ": half = " + std::to_string(half) + " is above GCWT_SMOOTH_MAX_HALF = " +
                                         std::to_string(kSmMaxHalf) + ": the kernel counts in columns, and an output_stride shortens it");
-    for (int32_t k = 0; k <= half; ++k)
-      if (!std::isfinite(taps[k])) return fail(GCWT_ERR_INVALID, op + ": taps[" + std::to_string(k) + "] must be finite");
+    rc = check_table(op.c_str(), "taps", taps, (int64_t)half + 1, Bound::kNone);
+    if (rc) return rc;
     if ((segments == nullptr) != (n_segments == 0) || n_segments < 0)
       return fail(GCWT_ERR_INVALID, op + ": segments and n_segments must be given together (NULL and 0: one segment, every column)");
     int64_t end = 0;                                         // where the segment before this one stops
@@ -86,25 +79,18 @@ int gcwt_trace_smooth(const float* d_trace, int64_t pitch, int64_t n_traces, int
     // one allocation: the taps w_1 .. (zeros up to a multiple of 4), the segments, the members
     std::vector<float> later((size_t)a.halo + kSmLaneCols, 0.f);          // (never empty)
     for (int32_t k = 1; k <= half; ++k) later[(size_t)k - 1] = taps[k];
-    const size_t at_segments = up16(later.size() * sizeof(float)), seg_bytes = (size_t)n_segments * 2 * sizeof(int64_t);
-    const size_t at_members = up16(at_segments + seg_bytes);
-    DeviceCopy work;
-    hipError_t e = work.alloc(at_members + (size_t)(n_members ? n_members : 1) * sizeof(int32_t));
-    if (e != hipSuccess) return fail(GCWT_ERR_NOMEM, op + ": no device memory for the taps and the segments: " + hipGetErrorString(e));
-    e = work.put(0, later.data(), later.size() * sizeof(float));
+    DeviceTable tab;
+    const size_t at_taps = tab.add(later.data(), later.size() * sizeof(float));
     static_assert(sizeof(longlong2) == 2 * sizeof(int64_t), "the (start, stop) pairs are copied as they are");
-    if (e == hipSuccess) e = work.put(at_segments, segments, seg_bytes);
-    if (e == hipSuccess && n_members) e = work.put(at_members, members, (size_t)n_members * sizeof(int32_t));
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e));
-    char* base = static_cast<char*>(work.p);
-    a.taps = reinterpret_cast<const float*>(base);
-    a.segments = reinterpret_cast<const longlong2*>(base + at_segments);
-    a.members = n_members ? reinterpret_cast<const int32_t*>(base + at_members) : nullptr;
+    const size_t at_segments = tab.add(segments, (size_t)n_segments * 2 * sizeof(int64_t), 16);
+    const size_t at_members = tab.add(members, (size_t)(n_members ? n_members : 1) * sizeof(int32_t), 16);
+    rc = tab.upload(op.c_str(), "the taps and the segments");
+    if (rc) return rc;
+    a.taps = tab.at<float>(at_taps);
+    a.segments = tab.at<longlong2>(at_segments);
+    a.members = n_members ? tab.at<int32_t>(at_members) : nullptr;
 
-    e = launch_trace_smooth(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);                // (the work arrays go when this returns)
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, op + ": " + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    return finish(op.c_str(), launch_trace_smooth(a, nullptr));           // (the tables go when this returns)
   });
 }
 

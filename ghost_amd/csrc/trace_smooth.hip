@@ -17,18 +17,12 @@
 // select, so a NaN or an inf beyond the end never enters.
 #include <hip/hip_runtime.h>
 
+#include "resident_op.h"
 #include "trace_smooth.h"
 
 namespace gcwt {
 
 namespace {
-
-// The taps, the segments and the members are written by the host before the launch and by nobody after it: read
-// through the constant address space, a wave-uniform index gives a scalar load.
-template <class T>
-using Const = const T __attribute__((address_space(4)))*;
-template <class T>
-__device__ __forceinline__ Const<T> constant(const T* p) { return (Const<T>)reinterpret_cast<uintptr_t>(p); }
 
 // the segment that holds column c, or an empty one
 __device__ __forceinline__ longlong2 segment_of(const SmoothArgs& a, int64_t c) {

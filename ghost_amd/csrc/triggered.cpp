@@ -92,23 +92,17 @@ int gcwt_triggered(const float* d_rows, int64_t pitch, int32_t n_channels, int32
     rc = resolve_device(kOp, d_rows, {d_amplitude, d_power, d_evoked, d_vector, d_itpc});
     if (rc) return rc;
 
-    DeviceCopy ev;
-    const size_t bytes = (size_t)n_events * sizeof(int64_t);
-    hipError_t e = ev.alloc(bytes);
-    if (e != hipSuccess)
-      return fail(GCWT_ERR_NOMEM, std::string("gcwt_triggered: no device memory for the event list: ") + hipGetErrorString(e));
-    e = ev.put(0, events, bytes);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_triggered: ") + hipGetErrorString(e));
+    DeviceTable tab;
+    const size_t at_events = tab.add(events, (size_t)n_events * sizeof(int64_t));
+    rc = tab.upload(kOp, "the event list");
+    if (rc) return rc;
 
     a.rows = reinterpret_cast<const float2*>(d_rows);
-    a.events = static_cast<const int64_t*>(ev.p);
+    a.events = tab.at<int64_t>(at_events);
     a.out_pitch = out_pitch;
     a.amplitude = d_amplitude; a.power = d_power; a.itpc = d_itpc;
     a.evoked = reinterpret_cast<float2*>(d_evoked); a.vector = reinterpret_cast<float2*>(d_vector);
-    e = gcwt::launch_triggered(a, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) return fail(GCWT_ERR_HIP, std::string("gcwt_triggered: ") + hipGetErrorString(e));
-    return (int)GCWT_OK;
+    return finish(kOp, gcwt::launch_triggered(a, nullptr));
   });
 }
 

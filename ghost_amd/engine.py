@@ -184,6 +184,16 @@ def coherence_pairs(pairs, seed, n_channels):
     return np.ascontiguousarray(arr, dtype=np.int32)
 
 
+def _is_number(v):
+    """A real number, Python's or numpy's, and no bool."""
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _ptr(arr, ctype):
+    """``arr`` as the C entries take an array of ``ctype``; None stays None."""
+    return None if arr is None else arr.ctypes.data_as(C.POINTER(ctype))
+
+
 def bin_window(window):
     """The bin width as an int: an integer >= 2 (numpy integers too); anything else raises ValueError."""
     if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
@@ -295,7 +305,7 @@ def coherence(result, pairs, window):
     return _run_into(
         res, "coherence", "%d pairs, %d channels, %d scales, %d bins" % (p, c, s, n_bins), "fewer pairs or a wider window",
         lambda ptr: check(lib.gcwt_coherence(result.buffer.ptr, result.pitch, c, s, n,
-                                             pairs.ctypes.data_as(C.POINTER(C.c_int32)), p, window, ptr["power"],
+                                             _ptr(pairs, C.c_int32), p, window, ptr["power"],
                                              ptr["cross"], ptr["coherence"], res.pitch)))
 
 
@@ -306,7 +316,7 @@ def coupling_rows(limits, frequencies, what):
     that anything else raises: not two finite numbers, f_lo > f_hi, no row inside."""
     try:
         ok = not isinstance(limits, (str, bytes)) and len(limits) == 2 and not any(
-            isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in limits)
+            not _is_number(v) for v in limits)
     except TypeError:
         ok = False
     if not ok or not all(np.isfinite(float(v)) for v in limits):
@@ -434,13 +444,12 @@ def coupling_surrogates(result, phase_rows, amp_rows, window, shifts, keep=False
         "narrower bands, a wider window or keep=False",
         lambda ptr: check(lib.gcwt_coupling_surrogates(result.buffer.ptr, result.pitch, c, s, n, phase_rows[0], phase_rows[1],
                                                        amp_rows[0], amp_rows[1], window,
-                                                       arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, ptr["mean"],
-                                                       ptr["sd"], ptr["count_ge"], ptr.get("surrogates"), res.pitch)))
+                                                       _ptr(arr, C.c_int64), arr.size, ptr["mean"], ptr["sd"],
+                                                       ptr["count_ge"], ptr.get("surrogates"), res.pitch)))
 
 
 def _seconds(value, what):
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(float(value)) or float(value) < 0:
+    if not _is_number(value) or not np.isfinite(float(value)) or float(value) < 0:
         raise ValueError("'%s' must be a finite number of seconds >= 0, not %r" % (what, value))
     return float(value)
 
@@ -548,8 +557,8 @@ def triggered(result, cols, nb, na, rows=None):
     return _run_into(
         res, "triggered", "%d channels, %d rows, %d lags" % (c, rows[1], n_lags), "fewer rows or a shorter window",
         lambda ptr: check(lib.gcwt_triggered(result.buffer.ptr, result.pitch, c, s, n, rows[0], rows[1],
-                                             arr.ctypes.data_as(C.POINTER(C.c_int64)), arr.size, nb, na, ptr["amplitude"],
-                                             ptr["power"], ptr["evoked"], ptr["vector"], ptr["itpc"], res.pitch)))
+                                             _ptr(arr, C.c_int64), arr.size, nb, na, ptr["amplitude"], ptr["power"],
+                                             ptr["evoked"], ptr["vector"], ptr["itpc"], res.pitch)))
 
 
 def band_rows(bands, frequencies):
@@ -614,14 +623,9 @@ def band_weights(frequencies, wavelet):
     return g.astype(np.float32), h.astype(np.float32)
 
 
-_BAND_OUTPUTS = (("analytic", np.complex64), ("envelope", np.float32), ("power", np.float32))
-
-
-class BandpassResult(_RowOpResult):
-    """What bandpass() left on the device, each (C, B, N) with rows ``pitch`` elements apart in one DeviceBuffer and only
-    those of ``outputs``: ``analytic`` complex64, ``envelope`` and ``power`` float32; ``rows``: (B, 2) of (first, count).
-    ``to_host()`` brings them over; until ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr +
-    _offsets()[name]``."""
+class _BandPlanes(_RowOpResult):
+    """Planes of (C, B, N), one row for each of the B bands of ``rows`` and only those of ``outputs``, which a subclass's
+    ``_OUTPUTS`` -- ((name, dtype), ...) in buffer order -- knows."""
 
     def __init__(self, buffer, n_channels, rows, n_cols, pitch, outputs):
         self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), rows, tuple(outputs)
@@ -629,11 +633,21 @@ class BandpassResult(_RowOpResult):
 
     def _planes(self):
         lead = (self.n_channels, self.n_bands)
-        return tuple((name, dtype, lead) for name, dtype in _BAND_OUTPUTS if name in self.outputs), self.n_cols
+        return tuple((name, dtype, lead) for name, dtype in self._OUTPUTS if name in self.outputs), self.n_cols
 
 
-def _band_outputs(outputs):
-    names = [name for name, _ in _BAND_OUTPUTS]
+class BandpassResult(_BandPlanes):
+    """What bandpass() left on the device, each (C, B, N) with rows ``pitch`` elements apart in one DeviceBuffer and only
+    those of ``outputs``: ``analytic`` complex64, ``envelope`` and ``power`` float32; ``rows``: (B, 2) of (first, count).
+    ``to_host()`` brings them over; until ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr +
+    _offsets()[name]``."""
+    _OUTPUTS = (("analytic", np.complex64), ("envelope", np.float32), ("power", np.float32))
+
+
+def _outputs(outputs, table):
+    """``outputs`` -- a name or a sequence of names of ``table`` = ((name, dtype), ...), at least one and each once -- as a
+    tuple."""
+    names = [name for name, _ in table]
     seq = (outputs,) if isinstance(outputs, str) else outputs
     try:
         ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
@@ -644,14 +658,43 @@ def _band_outputs(outputs):
     return tuple(seq)
 
 
-def _band_weight(w, n_scales, what, sign):
-    arr = np.asarray(w)
-    if arr.shape != (n_scales,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
-        raise ValueError("'%s' must hold one real weight for each of the result's %d rows" % (what, n_scales))
-    arr = np.ascontiguousarray(arr, dtype=np.float32)
-    if not np.all(np.isfinite(arr)) or (sign and np.any(arr < 0)):
-        raise ValueError("'%s' must be finite%s" % (what, " and at least 0" if sign else ""))
+def _band_table(rows, n_scales):
+    """``rows`` -- (B, 2) integers of (first, count), B >= 1, each a run of the result's ``n_scales`` rows -- as int32."""
+    arr = np.asarray(rows)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("rows must be a (B, 2) integer array of (first, count) with B >= 1, not %s of shape %r" % (arr.dtype, arr.shape))
+    return np.array([_row_range((int(a), int(b)), n_scales, "rows[%d]" % k) for k, (a, b) in enumerate(arr)], dtype=np.int32)
+
+
+def _real_table(v, n, what, noun, owner, bound=None, quiet=True):
+    """``v`` -- (n,) real numbers, one ``noun`` for each of ``owner`` -- as contiguous float32.  ``bound``: None, or what
+    besides finite every entry must be: "" (nothing), "at least 0", "above 0".  ``quiet``: a number beyond float32's
+    range becomes inf without numpy's overflow warning."""
+    arr = np.asarray(v)
+    if arr.shape != (n,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+        raise ValueError("'%s' must hold one real %s for each of %s" % (what, noun, owner))
+    with np.errstate(over="ignore" if quiet else None):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if bound is not None and (not np.all(np.isfinite(arr)) or (bound == "at least 0" and np.any(arr < 0))
+                              or (bound == "above 0" and np.any(arr <= 0))):
+        raise ValueError("'%s' must be finite%s" % (what, " and " + bound if bound else ""))
     return arr
+
+
+def _row_table(v, n_scales, what, noun, bound, quiet=True):
+    """_real_table for one entry per row of the result."""
+    return _real_table(v, n_scales, what, noun, "the result's %d rows" % n_scales, bound, quiet)
+
+
+def _hz_per_cycle(v):
+    """``v`` as the float32 the kernels take."""
+    if not _is_number(v):
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (v,))
+    with np.errstate(over="ignore"):
+        hz = np.float32(v)
+    if not np.isfinite(hz) or not hz > 0:
+        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (v,))
+    return float(hz)
 
 
 def bandpass(result, rows, g, h, outputs=("analytic", "envelope", "power")):
@@ -662,22 +705,17 @@ def bandpass(result, rows, g, h, outputs=("analytic", "envelope", "power")):
     Only the planes of ``outputs`` are allocated.  The result itself is only read.  -> BandpassResult, which stays on the
     device until ``to_host()`` / ``free()``."""
     c, s, n = _resident_complex(result, "bandpass", "a result sharded over several GPUs is not supported")
-    outputs = _band_outputs(outputs)
-    arr = np.asarray(rows)
-    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise ValueError("rows must be a (B, 2) integer array of (first, count) with B >= 1, not %s of shape %r" % (arr.dtype, arr.shape))
-    arr = np.array([_row_range((int(a), int(b)), s, "rows[%d]" % k) for k, (a, b) in enumerate(arr)], dtype=np.int32)
+    outputs = _outputs(outputs, BandpassResult._OUTPUTS)
+    arr = _band_table(rows, s)
     need_g, need_h = "analytic" in outputs or "envelope" in outputs, "power" in outputs
-    g = _band_weight(g, s, "g", False) if need_g else None
-    h = _band_weight(h, s, "h", True) if need_h else None
-    f32p = C.POINTER(C.c_float)
+    g = _row_table(g, s, "g", "weight", "", quiet=False) if need_g else None
+    h = _row_table(h, s, "h", "weight", "at least 0", quiet=False) if need_h else None
     res = BandpassResult(None, c, arr, n, _pitch(n), outputs)
     return _run_into(
         res, "bandpass", "%d channels, %d bands, %d columns, %s" % (c, len(arr), n, " + ".join(outputs)),
         "fewer bands or fewer outputs per call",
-        lambda ptr: check(lib.gcwt_bandpass(result.buffer.ptr, result.pitch, c, s, n, arr.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            len(arr), None if g is None else g.ctypes.data_as(f32p),
-                                            None if h is None else h.ctypes.data_as(f32p), ptr.get("analytic"),
+        lambda ptr: check(lib.gcwt_bandpass(result.buffer.ptr, result.pitch, c, s, n, _ptr(arr, C.c_int32), len(arr),
+                                            _ptr(g, C.c_float), _ptr(h, C.c_float), ptr.get("analytic"),
                                             ptr.get("envelope"), ptr.get("power"), res.pitch)))
 
 
@@ -710,45 +748,12 @@ def ridge_weights(frequencies, wavelet):
     return e.astype(np.float32)
 
 
-_RIDGE_OUTPUTS = (("row", np.int32), ("amplitude", np.float32), ("offset", np.float32), ("frequency", np.float32))
-
-
-class RidgeResult(_RowOpResult):
+class RidgeResult(_BandPlanes):
     """What ridge() left on the device, each (C, B, N) with rows ``pitch`` elements apart in one DeviceBuffer and only
     those of ``outputs``: ``row`` int32, ``amplitude``, ``offset`` and ``frequency`` float32; ``rows``: (B, 2) of (first,
     count).  ``to_host()`` brings them over; until ``free()`` a device-side consumer finds plane ``name`` at ``buffer.ptr
     + _offsets()[name]``."""
-
-    def __init__(self, buffer, n_channels, rows, n_cols, pitch, outputs):
-        self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), rows, tuple(outputs)
-        self.n_channels, self.n_bands, self.n_cols = int(n_channels), len(rows), int(n_cols)
-
-    def _planes(self):
-        lead = (self.n_channels, self.n_bands)
-        return tuple((name, dtype, lead) for name, dtype in _RIDGE_OUTPUTS if name in self.outputs), self.n_cols
-
-
-def _ridge_outputs(outputs):
-    names = [name for name, _ in _RIDGE_OUTPUTS]
-    seq = (outputs,) if isinstance(outputs, str) else outputs
-    try:
-        ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
-    except TypeError:
-        ok = False
-    if not ok:
-        raise ValueError("'outputs' must name at least one of %s, each once, not %r" % (", ".join(names), outputs))
-    return tuple(seq)
-
-
-def _ridge_table(w, n_scales, what, strict):
-    arr = np.asarray(w)
-    if arr.shape != (n_scales,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
-        raise ValueError("'%s' must hold one real number for each of the result's %d rows" % (what, n_scales))
-    with np.errstate(over="ignore"):
-        arr = np.ascontiguousarray(arr, dtype=np.float32)
-    if not np.all(np.isfinite(arr)) or np.any(arr <= 0 if strict else arr < 0):
-        raise ValueError("'%s' must be finite and %s" % (what, "above 0" if strict else "at least 0"))
-    return arr
+    _OUTPUTS = (("row", np.int32), ("amplitude", np.float32), ("offset", np.float32), ("frequency", np.float32))
 
 
 def _ridge_segments(segments, n_cols):
@@ -779,29 +784,20 @@ def ridge(result, rows, e, nu, hz_per_cycle, segments, outputs=("row", "amplitud
     Only the planes of ``outputs`` are allocated.  The result itself is only read.  -> RidgeResult, which stays on the
     device until ``to_host()`` / ``free()``."""
     c, s, n = _resident_complex(result, "ridge", "a result sharded over several GPUs is not supported")
-    outputs = _ridge_outputs(outputs)
-    arr = np.asarray(rows)
-    if arr.ndim != 2 or arr.shape[1] != 2 or arr.shape[0] < 1 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise ValueError("rows must be a (B, 2) integer array of (first, count) with B >= 1, not %s of shape %r" % (arr.dtype, arr.shape))
-    arr = np.array([_row_range((int(a), int(b)), s, "rows[%d]" % k) for k, (a, b) in enumerate(arr)], dtype=np.int32)
-    e = _ridge_table(e, s, "e", True)
-    nu = _ridge_table(nu, s, "nu", False)
-    if isinstance(hz_per_cycle, (bool, np.bool_)) or not isinstance(hz_per_cycle, (int, float, np.integer, np.floating)):
-        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
-    with np.errstate(over="ignore"):
-        hz = np.float32(hz_per_cycle)
-    if not np.isfinite(hz) or not hz > 0:
-        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    outputs = _outputs(outputs, RidgeResult._OUTPUTS)
+    arr = _band_table(rows, s)
+    e = _row_table(e, s, "e", "number", "above 0")
+    nu = _row_table(nu, s, "nu", "number", "at least 0")
+    hz = _hz_per_cycle(hz_per_cycle)
     seg = _ridge_segments(segments, n)
-    f32p = C.POINTER(C.c_float)
     res = RidgeResult(None, c, arr, n, _pitch(n), outputs)
     return _run_into(
         res, "ridge", "%d channels, %d bands, %d columns, %s" % (c, len(arr), n, " + ".join(outputs)),
         "fewer bands or fewer outputs per call",
-        lambda ptr: check(lib.gcwt_ridge(result.buffer.ptr, result.pitch, c, s, n, arr.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         len(arr), e.ctypes.data_as(f32p), nu.ctypes.data_as(f32p), float(hz),
-                                         seg.ctypes.data_as(C.POINTER(C.c_int64)), len(seg), ptr.get("row"),
-                                         ptr.get("amplitude"), ptr.get("offset"), ptr.get("frequency"), res.pitch)))
+        lambda ptr: check(lib.gcwt_ridge(result.buffer.ptr, result.pitch, c, s, n, _ptr(arr, C.c_int32), len(arr),
+                                         _ptr(e, C.c_float), _ptr(nu, C.c_float), hz, _ptr(seg, C.c_int64), len(seg),
+                                         ptr.get("row"), ptr.get("amplitude"), ptr.get("offset"), ptr.get("frequency"),
+                                         res.pitch)))
 
 
 def squeeze_edges(centres):
@@ -837,9 +833,6 @@ def squeeze_edges(centres):
     return edges, descending
 
 
-_SQUEEZE_OUTPUTS = (("coefficients", np.complex64), ("power", np.float32), ("frequency", np.float32), ("index", np.int32))
-
-
 class SqueezeResult(_RowOpResult):
     """What squeeze() left on the device, rows ``pitch`` elements apart in one DeviceBuffer and only those of ``outputs``:
     ``coefficients`` complex64 and ``power`` float32, each (C, L, N) over the L cells; ``frequency`` float32 and ``index``
@@ -850,22 +843,12 @@ class SqueezeResult(_RowOpResult):
         self.buffer, self.pitch, self.rows, self.outputs = buffer, int(pitch), tuple(rows), tuple(outputs)
         self.n_channels, self.n_rows, self.n_cells, self.n_cols = int(n_channels), int(rows[1]), int(n_cells), int(n_cols)
 
+    _OUTPUTS = (("coefficients", np.complex64), ("power", np.float32), ("frequency", np.float32), ("index", np.int32))
+
     def _planes(self):
         lead = {"coefficients": (self.n_channels, self.n_cells), "power": (self.n_channels, self.n_cells),
                 "frequency": (self.n_channels, self.n_rows), "index": (self.n_channels, self.n_rows)}
-        return tuple((name, dtype, lead[name]) for name, dtype in _SQUEEZE_OUTPUTS if name in self.outputs), self.n_cols
-
-
-def _squeeze_outputs(outputs):
-    names = [name for name, _ in _SQUEEZE_OUTPUTS]
-    seq = (outputs,) if isinstance(outputs, str) else outputs
-    try:
-        ok = len(seq) >= 1 and all(isinstance(v, str) and v in names for v in seq) and len(set(seq)) == len(seq)
-    except TypeError:
-        ok = False
-    if not ok:
-        raise ValueError("'outputs' must name at least one of %s, each once, not %r" % (", ".join(names), outputs))
-    return tuple(seq)
+        return tuple((name, dtype, lead[name]) for name, dtype in self._OUTPUTS if name in self.outputs), self.n_cols
 
 
 def _squeeze_cells(edges):
@@ -896,31 +879,25 @@ def squeeze(result, rows, g, floor2, nu, hz_per_cycle, segments, edges, descendi
     are allocated.  The result itself is only read.  -> SqueezeResult, which stays on the device until ``to_host()`` /
     ``free()``."""
     c, s, n = _resident_complex(result, "squeeze", "a result sharded over several GPUs is not supported")
-    outputs = _squeeze_outputs(outputs)
+    outputs = _outputs(outputs, SqueezeResult._OUTPUTS)
     first, count = _row_range(rows, s, "rows")
-    g = _band_weight(g, s, "g", False)
-    floor2 = _ridge_table(floor2, s, "floor2", False)
-    nu = _ridge_table(nu, s, "nu", False)
-    if isinstance(hz_per_cycle, (bool, np.bool_)) or not isinstance(hz_per_cycle, (int, float, np.integer, np.floating)):
-        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
-    with np.errstate(over="ignore"):
-        hz = np.float32(hz_per_cycle)
-    if not np.isfinite(hz) or not hz > 0:
-        raise ValueError("'hz_per_cycle' must be a finite number above 0 (fs / K), not %r" % (hz_per_cycle,))
+    g = _row_table(g, s, "g", "weight", "", quiet=False)
+    floor2 = _row_table(floor2, s, "floor2", "number", "at least 0")
+    nu = _row_table(nu, s, "nu", "number", "at least 0")
+    hz = _hz_per_cycle(hz_per_cycle)
     seg = _ridge_segments(segments, n)
     edges = _squeeze_cells(edges)
     if not isinstance(descending, (bool, np.bool_)):
         raise ValueError("'descending' must be True or False, not %r" % (descending,))
-    f32p = C.POINTER(C.c_float)
     res = SqueezeResult(None, c, (first, count), edges.size - 1, n, _pitch(n), outputs)
     return _run_into(
         res, "squeeze", "%d channels, %d cells, %d rows, %d columns, %s" % (c, edges.size - 1, count, n, " + ".join(outputs)),
         "fewer cells, fewer outputs or an output_stride",
-        lambda ptr: check(lib.gcwt_squeeze(result.buffer.ptr, result.pitch, c, s, n, first, count, g.ctypes.data_as(f32p),
-                                           floor2.ctypes.data_as(f32p), nu.ctypes.data_as(f32p), float(hz),
-                                           seg.ctypes.data_as(C.POINTER(C.c_int64)), len(seg), edges.ctypes.data_as(f32p),
-                                           edges.size - 1, int(bool(descending)), ptr.get("coefficients"), ptr.get("power"),
-                                           ptr.get("frequency"), ptr.get("index"), res.pitch)))
+        lambda ptr: check(lib.gcwt_squeeze(result.buffer.ptr, result.pitch, c, s, n, first, count, _ptr(g, C.c_float),
+                                           _ptr(floor2, C.c_float), _ptr(nu, C.c_float), hz, _ptr(seg, C.c_int64), len(seg),
+                                           _ptr(edges, C.c_float), edges.size - 1, int(bool(descending)),
+                                           ptr.get("coefficients"), ptr.get("power"), ptr.get("frequency"), ptr.get("index"),
+                                           res.pitch)))
 
 
 def _traces(buffer_ptr, pitch, n_traces, n_cols, what):
@@ -941,9 +918,7 @@ def trace_stats(buffer_ptr, pitch, n_traces, n_cols):
     float64, sd float64), each (n_traces,); mean and sd are 0 where n is.  Three numbers per trace cross to the host."""
     ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_stats")
     n, mean, sd = np.zeros(max(n_traces, 0), np.int64), np.zeros(max(n_traces, 0)), np.zeros(max(n_traces, 0))
-    f64p = C.POINTER(C.c_double)
-    check(lib.gcwt_trace_stats(ptr, pitch, n_traces, n_cols, n.ctypes.data_as(C.POINTER(C.c_int64)), mean.ctypes.data_as(f64p),
-                               sd.ctypes.data_as(f64p)))
+    check(lib.gcwt_trace_stats(ptr, pitch, n_traces, n_cols, _ptr(n, C.c_int64), _ptr(mean, C.c_double), _ptr(sd, C.c_double)))
     return n, mean, sd
 
 
@@ -958,16 +933,12 @@ def trace_runs(buffer_ptr, pitch, n_traces, n_cols, lo):
     the columns [start, stop)), ``peak_col`` int64 (the first column that holds the largest value), ``peak`` float32;
     and ``counts`` (n_traces,) int64: the runs of each trace.  28 bytes per run cross to the host."""
     ptr, pitch, n_traces, n_cols = _traces(buffer_ptr, pitch, n_traces, n_cols, "trace_runs")
-    arr = np.asarray(lo)
-    if arr.shape != (n_traces,) or arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
-        raise ValueError("'lo' must hold one real threshold for each of the %d traces" % n_traces)
-    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    arr = _real_table(lo, n_traces, "lo", "threshold", "the %d traces" % n_traces, quiet=False)
     counts = np.zeros(n_traces, np.int64)
-    i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
 
     def call(capacity, where):
-        check(lib.gcwt_trace_runs(ptr, pitch, n_traces, n_cols, arr.ctypes.data_as(f32p), capacity, where["start"], where["stop"],
-                                  where["peak_col"], where["peak"], counts.ctypes.data_as(i64p)))
+        check(lib.gcwt_trace_runs(ptr, pitch, n_traces, n_cols, _ptr(arr, C.c_float), capacity, where["start"], where["stop"],
+                                  where["peak_col"], where["peak"], _ptr(counts, C.c_int64)))
 
     call(0, dict.fromkeys((name for name, _ in _RUN_FIELDS)))
     total = int(counts.sum())
@@ -1015,18 +986,14 @@ def trace_order(buffer_ptr, pitch, n_traces, n_cols, ranks, center=None):
     if arr.size and int(arr.min()) < 0:
         raise ValueError("'ranks' must be at least 0, not %d" % int(arr.min()))
     arr = np.ascontiguousarray(arr, dtype=np.int64)
-    f32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    cen = None
     if center is not None:
-        cen = np.asarray(center)
-        if cen.shape != (n_traces,) or cen.dtype == np.bool_ or not (np.issubdtype(cen.dtype, np.floating) or np.issubdtype(cen.dtype, np.integer)):
-            raise ValueError("'center' must hold one real value for each of the %d traces" % n_traces)
-        with np.errstate(over="ignore"):
-            cen = np.ascontiguousarray(cen, dtype=np.float32)
+        cen = _real_table(center, n_traces, "center", "value", "the %d traces" % n_traces)
         if not np.all(np.isfinite(cen)):
             raise ValueError("'center' must be finite in float32")
     n, values = np.zeros(arr.shape[0], np.int64), np.zeros(arr.shape, np.float32)
-    check(lib.gcwt_trace_order(ptr, pitch, n_traces, n_cols, None if center is None else cen.ctypes.data_as(f32p),
-                               arr.ctypes.data_as(i64p), arr.shape[1], n.ctypes.data_as(i64p), values.ctypes.data_as(f32p)))
+    check(lib.gcwt_trace_order(ptr, pitch, n_traces, n_cols, _ptr(cen, C.c_float), _ptr(arr, C.c_int64), arr.shape[1],
+                               _ptr(n, C.c_int64), _ptr(values, C.c_float)))
     return n, values
 
 
@@ -1060,8 +1027,7 @@ def smooth_taps(sd_cols):
     sd_cols^2)) for k = 0 .. half, normalised in float64 so that w_0 + 2 sum w_k = 1 and then rounded to float32 once.
     -> float32 (half + 1,).  ValueError where half is 0 (the window is narrower than a column) or above
     _lib.SMOOTH_MAX_HALF (the window counts in columns: an output stride shortens it)."""
-    if isinstance(sd_cols, (bool, np.bool_)) or not isinstance(sd_cols, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(float(sd_cols)) or float(sd_cols) <= 0:
+    if not _is_number(sd_cols) or not np.isfinite(float(sd_cols)) or float(sd_cols) <= 0:
         raise ValueError("'sd_cols' must be a finite number of columns > 0, not %r" % (sd_cols,))
     sd = float(sd_cols)
     half = int(4 * sd + 0.5) if 4 * sd + 0.5 < 2.0 ** 62 else 2 ** 62
@@ -1124,9 +1090,8 @@ def trace_smooth(buffer_ptr, pitch, n_traces, n_cols, taps, segments=None, membe
             raise ValueError("'members' must name traces 0 .. %d, not %d" % (n_traces - 1, mem.min() if mem.min() < 0 else mem.max()))
         mem = np.ascontiguousarray(mem, dtype=np.int32)
     n_out, out_pitch = (n_traces if mem is None else 1), _pitch(max(n_cols, 1))
-    args = (ptr, pitch, n_traces, n_cols, w.ctypes.data_as(C.POINTER(C.c_float)), w.size - 1,
-            None if seg is None else seg.ctypes.data_as(C.POINTER(C.c_int64)), 0 if seg is None else len(seg),
-            None if mem is None else mem.ctypes.data_as(C.POINTER(C.c_int32)), 0 if mem is None else mem.size)
+    args = (ptr, pitch, n_traces, n_cols, _ptr(w, C.c_float), w.size - 1, _ptr(seg, C.c_int64), 0 if seg is None else len(seg),
+            _ptr(mem, C.c_int32), 0 if mem is None else mem.size)
     if n_out < 1 or n_cols < 1:
         check(lib.gcwt_trace_smooth(*args, None, out_pitch))        # (refused in the library's words)
     nbytes = n_out * out_pitch * 4

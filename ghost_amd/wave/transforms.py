@@ -114,12 +114,23 @@ class _Events:
         return len(self.channel)
 
 
+def _fetched(res, squeeze=False):
+    """The planes an engine operator left on the device, as host arrays -- without the channel axis where ``squeeze`` --;
+    the device's copy is freed."""
+    try:
+        out = res.to_host()
+    finally:
+        res.free()
+    return {k: v[0] for k, v in out.items()} if squeeze else out
+
+
 def _baseline_columns(baseline, time, n_cols, period):
     """detect()'s ``baseline=(t0, t1)`` -> the columns [c0, c1) with t0 <= time < t1; ``time``: the columns' times or
     None (column j at j ``period``).  ValueError for anything but one non-empty stretch."""
+    from .. import engine
     try:
         t0, t1 = baseline
-        ok = all(not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) for v in (t0, t1))
+        ok = all(engine._is_number(v) for v in (t0, t1))
     except (TypeError, ValueError):
         ok = False
     if not ok or not (np.isfinite(float(t0)) and np.isfinite(float(t1))):
@@ -435,6 +446,15 @@ class ContinuousWaveletTransform(WaveletTransform):
                              "(devices=[...]), %s" % (what, one_device, sharded))
         return self._device_result, squeeze
 
+    def _phase_clock(self, f, n_cols):
+        """What ridge() and squeeze() turn a phase advance into a frequency with, for rows at ``f`` Hz and ``n_cols``
+        columns: (the columns' times or None, nu = 2 pi f K / fs, hz_per_cycle = fs / K, the segments of the clock)."""
+        from .. import engine
+        stride, fs = self._stride, float(self._fs)
+        t = self.time
+        t = None if t is None else np.asarray(t)
+        return t, 2 * np.pi * f * stride / fs, fs / stride, engine.segments_of(t, stride / fs, fs, n_cols)
+
     def coherence(self, pairs=None, *, seed=None, window):
         """Wavelet coherence and cross-spectra between channels of the last transform, reduced on the device over bins
         of ``window`` columns (an integer >= 2; with an output stride K a column is K samples) -- the transform must
@@ -456,11 +476,7 @@ class ContinuousWaveletTransform(WaveletTransform):
             raise ValueError("coherence() relates channels: the last transform must be multichannel=True with at "
                              "least 2 channels")
         pairs = engine.coherence_pairs(pairs, seed, result.shape[0])
-        res = engine.coherence(result, pairs, window)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
+        out = _fetched(engine.coherence(result, pairs, window))
         t = self.time
         return _Coherence(out["coherence"], out["cross"], out["power"], pairs.astype(np.int64),
                           np.array(self._frequencies), None if t is None else np.asarray(t)[::window], window)
@@ -513,23 +529,14 @@ class ContinuousWaveletTransform(WaveletTransform):
             if min_shift is None:
                 min_cols = int(np.ceil(float(self._fs) / (self._stride * float(f_phase.min()))))
             else:
-                if isinstance(min_shift, (bool, np.bool_)) or not isinstance(min_shift, (int, float, np.integer, np.floating)) \
-                        or not np.isfinite(float(min_shift)) or float(min_shift) <= 0:
+                if not engine._is_number(min_shift) or not np.isfinite(float(min_shift)) or float(min_shift) <= 0:
                     raise ValueError("coupling(): 'min_shift' must be a finite number of seconds > 0, not %r" % (min_shift,))
                 min_cols = max(1, int(np.ceil(float(min_shift) / per_col)))
             shifts = engine.surrogate_shifts(surrogates, window, min_cols, seed)
-        res = engine.coupling(result, phase_rows, amp_rows, window)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
+        out = _fetched(engine.coupling(result, phase_rows, amp_rows, window))
         stats = None
         if shifts is not None:
-            res = engine.coupling_surrogates(result, phase_rows, amp_rows, window, shifts, keep=keep_surrogates)
-            try:
-                stats = res.to_host()
-            finally:
-                res.free()
+            stats = _fetched(engine.coupling_surrogates(result, phase_rows, amp_rows, window, shifts, keep=keep_surrogates))
             mean, sd = stats["mean"].astype(np.float64), stats["sd"].astype(np.float64)
             stats["z"] = np.where(sd > 0, (out["mvl"].astype(np.float64) - mean) / np.where(sd > 0, sd, 1.0), 0.0).astype(np.float32)
             stats["p"] = ((1.0 + stats.pop("count_ge")) / (shifts.size + 1.0)).astype(np.float32)
@@ -573,13 +580,7 @@ class ContinuousWaveletTransform(WaveletTransform):
                              "the recording, %d have a window (%d columns before, %d after) that leaves the recording, "
                              "%d have a window that would splice two epochs"
                              % (used.size, why["gap"], why["edge"], nb, na, why["splice"]))
-        res = engine.triggered(result, cols, nb, na, rows)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
-        if squeeze:
-            out = {k: v[0] for k, v in out.items()}
+        out = _fetched(engine.triggered(result, cols, nb, na, rows), squeeze)
         return _Triggered(out["amplitude"], out["power"], out["evoked"], out["vector"], out["itpc"],
                           np.arange(-nb, na + 1) * stride / fs, f[rows[0]:rows[0] + rows[1]], used, int(cols.size))
 
@@ -610,13 +611,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         f = np.array(self._frequencies)
         rows = engine.band_rows(bands, f)
         g, h = engine.band_weights(f, self._wavelet)
-        res = engine.bandpass(result, rows, g, h, outputs)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
-        if squeeze:
-            out = {k: v[0] for k, v in out.items()}
+        out = _fetched(engine.bandpass(result, rows, g, h, outputs), squeeze)
         t = self.time
         return _Bandpass(out.get("analytic"), out.get("envelope"), out.get("power"),
                          np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
@@ -652,18 +647,9 @@ class ContinuousWaveletTransform(WaveletTransform):
         result, squeeze = self._resident_rows("ridge")
         f = np.array(self._frequencies)
         rows = engine.band_rows(bands, f)
-        stride, fs = self._stride, float(self._fs)
-        t = self.time
-        t = None if t is None else np.asarray(t)
-        segments = engine.segments_of(t, stride / fs, fs, result.shape[2])
-        res = engine.ridge(result, rows, engine.ridge_weights(f, self._wavelet), 2 * np.pi * f * stride / fs, fs / stride,
-                           segments, outputs)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
-        if squeeze:
-            out = {k: v[0] for k, v in out.items()}
+        t, nu, hz_per_cycle, segments = self._phase_clock(f, result.shape[2])
+        out = _fetched(engine.ridge(result, rows, engine.ridge_weights(f, self._wavelet), nu, hz_per_cycle, segments, outputs),
+                       squeeze)
         return _Ridge(out.get("row"), out.get("amplitude"), out.get("frequency"), out.get("offset"),
                       np.asarray(bands, dtype=np.float64).reshape(-1, 2), rows.astype(np.int64),
                       [f[a:a + n] for a, n in rows], t, f)
@@ -704,8 +690,7 @@ class ContinuousWaveletTransform(WaveletTransform):
         f = np.array(self._frequencies)
         rows = (0, f.size) if freq_limits is None else engine.coupling_rows(freq_limits, f, "freq_limits")
         own = f[rows[0]:rows[0] + rows[1]]
-        if isinstance(min_amplitude, (bool, np.bool_)) or not isinstance(min_amplitude, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(float(min_amplitude)) or float(min_amplitude) < 0:
+        if not engine._is_number(min_amplitude) or not np.isfinite(float(min_amplitude)) or float(min_amplitude) < 0:
             raise ValueError("squeeze(): 'min_amplitude' must be a finite number, at least 0, not %r" % (min_amplitude,))
         if bins is None or (isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_))):
             if own.size < 2:
@@ -728,18 +713,9 @@ class ContinuousWaveletTransform(WaveletTransform):
             floor2 = (np.square(np.float64(min_amplitude)) / e).astype(np.float32)
         if not np.all(np.isfinite(floor2)):
             raise ValueError("squeeze(): 'min_amplitude' = %r squared leaves float32's range" % (min_amplitude,))
-        stride, fs = self._stride, float(self._fs)
-        t = self.time
-        t = None if t is None else np.asarray(t)
-        segments = engine.segments_of(t, stride / fs, fs, result.shape[2])
-        res = engine.squeeze(result, rows, engine.band_weights(f, self._wavelet)[0], floor2, 2 * np.pi * f * stride / fs,
-                             fs / stride, segments, edges, descending, outputs)
-        try:
-            out = res.to_host()
-        finally:
-            res.free()
-        if squeeze:
-            out = {k: v[0] for k, v in out.items()}
+        t, nu, hz_per_cycle, segments = self._phase_clock(f, result.shape[2])
+        out = _fetched(engine.squeeze(result, rows, engine.band_weights(f, self._wavelet)[0], floor2, nu, hz_per_cycle, segments,
+                                      edges, descending, outputs), squeeze)
         return _Squeeze(out.get("coefficients"), out.get("power"), out.get("frequency"), out.get("index"), centres, edges,
                         (int(rows[0]), int(rows[1])), own, t, float(min_amplitude))
 
@@ -813,8 +789,7 @@ class ContinuousWaveletTransform(WaveletTransform):
                              "single-channel call")
         taps = None
         if smooth is not None:
-            if isinstance(smooth, (bool, np.bool_)) or not isinstance(smooth, (int, float, np.integer, np.floating)) \
-                    or not np.isfinite(float(smooth)) or float(smooth) <= 0:
+            if not engine._is_number(smooth) or not np.isfinite(float(smooth)) or float(smooth) <= 0:
                 raise ValueError("detect(): 'smooth' must be None or a finite number of seconds > 0, not %r" % (smooth,))
             smooth = float(smooth)
             try:
@@ -822,7 +797,7 @@ class ContinuousWaveletTransform(WaveletTransform):
             except ValueError as e:
                 raise ValueError("detect(): 'smooth' = %g s at %g columns per second: %s" % (smooth, float(self._fs) / self._stride, e)) from None
         for name, v in (("threshold", threshold), ("edge", edge)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+            if not engine._is_number(v) or not np.isfinite(float(v)):
                 raise ValueError("detect(): '%s' must be a finite number, not %r" % (name, v))
         threshold, edge = float(threshold), float(edge)
         if threshold < edge:
